@@ -11,6 +11,12 @@ rank owns its own document: SURVEY.md §8e).
 
     python bench.py [--gpus N --steps K --warmup W]      # N > 1: launches N ranks itself
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (the phase
+rooflines in it come from the timed steps' own event timings).  ``--full`` adds, after the
+timed steps, the output self-checks, one extra HIP-event-timed step for the roofline of the
+dominant decode kernel, and the torch-CPU baseline.  ``--dump-outputs DIR`` writes what the
+last timed step returned as DIR/summary_rows.npy.
 """
 from __future__ import annotations
 
@@ -198,6 +204,18 @@ def pmc_traffic(weights, B, prompt_len, kernel="gemv"):
     return None, None
 
 
+def dump_outputs(out_dir, rows):
+    """--dump-outputs: what the last timed step handed its caller, the gathered summary rows
+    (dist.pack_results: doc, chunk, n, ids zero padded; rows of padding have n == -1), as
+    out_dir/summary_rows.npy.  float32 holds every token id exactly (vocab < 2^24).  The
+    inputs are seeded (synthetic weights and chunks), so two builds run with the same
+    arguments are comparable row for row."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.asarray(rows, np.float32)
+    a = a[:(64 << 20) // (4 * a.shape[1])]  # at most 64 MB: ~1 KB per chunk at 256 summary tokens
+    np.save(os.path.join(out_dir, "summary_rows.npy"), a)
+
+
 def _spawn_ranks(n):
     """`python bench.py --gpus N` outside torchrun: start N ranks (one per GPU) as
     children through torch.distributed.run, before this process touches any GPU, and
@@ -229,9 +247,15 @@ def parse_args(argv=None):
     ap.add_argument("--eos", type=int, default=0,
                     help="natural-EOS mode: stop at a synthetic set of N stop ids (seeded) instead of "
                          "ignore_eos, so chunks finish at varied lengths and slots turn over")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip HIP-event timing of the GEMV class")
-    ap.add_argument("--no-check", action="store_true", help="skip the output self-checks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the output self-checks, the HIP-event roofline "
+                         "step of the dominant kernel and the torch-CPU baseline (each has its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the torch-CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="--full: skip HIP-event timing of the GEMV class")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the output self-checks")
     ap.add_argument("--bcast-weights", action="store_true",
                     help="N > 1: rank 0 makes the weights, the other ranks receive them over RCCL")
     return ap.parse_args(argv)
@@ -335,10 +359,13 @@ def main():
     value = total_chunks / dt
     assert rows is not None and int((rows[:, 2] >= 0).sum()) == total_chunks // args.steps
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rows)
+
     # self-checks (outside the timed region): every step produced the same summaries, each
     # of the full length, and a chunk's summary does not depend on its batch companions
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         same = all(o == outs[0] for o in outs[1:])
         full = all(len(ids) == args.gen_len for ids in outs[0]) or not ignore_eos
         alone = eng.generate([chunks[0]], num_predict=args.gen_len, ignore_eos=ignore_eos)[0].ids
@@ -347,7 +374,7 @@ def main():
         assert same and full and check["batch_invariant_chunk0"], check
 
     roof = roof_lm = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # Roofline of the dominant kernel: one more map step with HIP events bracketing every
         # decode launch of its class on the engine's stream (an event pair per launch would
         # distort `value`, so this runs after the timed region).  Engines of <= 8 slots on fp16
@@ -455,7 +482,7 @@ def main():
         "cpu_baseline": None,
     }
     note(f"timed {args.steps} step(s): {value:.3f} chunks/s")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         eng.close()
         out["cpu_baseline"] = cpu_baseline(cfg, chunks[0], args.gen_len)
     eng.close()

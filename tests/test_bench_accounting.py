@@ -2,6 +2,8 @@
 import importlib.util
 import os
 
+import numpy as np
+
 from mapsum.config import LLAMA32_3B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,3 +124,25 @@ def test_pmc_traffic_matches_rows_and_regime():
     assert src128 and src128.endswith("pmc_traffic_f16_b128.json") and t128 > t8
     assert bench.pmc_traffic("f16", 64, 2048) == (None, None)  # no pass at 64 rows
     assert bench.pmc_traffic("f16", 8, 1024) == (None, None)
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    """A plain run only times its steps: the self-checks, the roofline step and the CPU baseline
+    run under --full alone, where their --no-* switches still apply."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.dump_outputs is None and (plain.steps, plain.warmup) == (7, 2)
+    full = bench.parse_args(["--full", "--no-cpu-baseline", "--dump-outputs", "d"])
+    assert full.full and full.no_cpu_baseline and not full.no_check and full.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_the_gathered_rows_as_float32(tmp_path):
+    from mapsum.dist import Unit, pack_results
+    rows = pack_results([Unit(0, 0, 8), Unit(2, 1, 8)], [[5, 6, 128255], [1]], 4)
+    out = tmp_path / "a" / "b"  # created on demand
+    bench.dump_outputs(str(out), rows)
+    assert os.listdir(out) == ["summary_rows.npy"]
+    a = np.load(out / "summary_rows.npy")
+    assert a.dtype == np.float32 and a.shape == rows.shape
+    assert np.array_equal(a.astype(np.int32), rows)  # every id is exact in float32
+    bench.dump_outputs(str(out), rows)  # a second run with the same arguments overwrites in place
+    assert np.array_equal(np.load(out / "summary_rows.npy"), a)

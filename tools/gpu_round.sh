@@ -12,7 +12,7 @@ if [ -z "$SKIP_TESTS" ]; then
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1 || { tail -40 $O/gpu_tests.log; exit 1; }
 tail -3 $O/gpu_tests.log
 fi
-timeout -k 10 400 python -u bench.py "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { tail -30 $O/bench_$TAG.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { tail -30 $O/bench_$TAG.err; exit 1; }
 cat $O/bench_$TAG.json
 # the profiled run is the timed workload only: no self-check / roofline extra steps (their
 # B=1 rerun and event-bracketed step would fold other batch shapes into the averages)
