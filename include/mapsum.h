@@ -170,12 +170,38 @@ int ms_declare_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t ggm
 /* ---- request path (replaces one /api/generate per chunk) -------------------- */
 int ms_submit(ms_engine* e, const int32_t* ids, int32_t n, int32_t num_predict,
               uint32_t flags, uint64_t tag);
+/* Sampled decoding (Ollama's `options`; DESIGN.md "Sampler").  Per generated token, on the row's
+ * fp32 logits: repeat penalty over the distinct ids among the last repeat_last_n of prompt +
+ * generated tokens (l > 0 ? l / rp : l * rp) -> the top_k largest (ties to the lowest id) ->
+ * top_p (the shortest prefix of softmax at T = 1 reaching it; >= 1 off) -> min_p (l >= l_max +
+ * ln(min_p); <= 0 off) -> softmax(l / temperature) -> the first candidate, in (logit desc, id asc)
+ * order, whose cumulative probability exceeds
+ *     u(seed, step) = (mix64(mix64(seed) + 0x9E3779B97F4A7C15 * (step + 1)) >> 40) * 2^-24,
+ * step = the index of the generated token.  The ids depend on nothing else: not on the slot, the
+ * other chunks of the batch or how ms_step chunks the decode runs.  The order is llama.cpp's
+ * sampler chain; the random numbers are this engine's own, not Ollama's generator.
+ * temperature <= 0: greedy, every other field ignored. */
+#define MS_SAMPLE_MAX_TOPK 256
+#define MS_SAMPLE_MAX_WINDOW 256
+typedef struct ms_sampling {
+  float temperature;      /* <= 0: greedy                                         */
+  int32_t top_k;          /* 1 .. MS_SAMPLE_MAX_TOPK (<= 0, "whole vocabulary", is refused) */
+  float top_p;            /* > 0                                                  */
+  float min_p;            /* 0 <= min_p < 1                                       */
+  float repeat_penalty;   /* > 0; 1 = off                                         */
+  int32_t repeat_last_n;  /* 0 .. MS_SAMPLE_MAX_WINDOW; 0 = off                   */
+  uint64_t seed;
+} ms_sampling;
+/* ms_submit with sampling; sp == NULL or sp->temperature <= 0 is exactly ms_submit.  A field out
+   of range is MS_EINVAL with a message that names it. */
+int ms_submit_sampled(ms_engine* e, const int32_t* ids, int32_t n, int32_t num_predict,
+                      uint32_t flags, uint64_t tag, const ms_sampling* sp);
 /* replace the config's end-of-turn ids by a larger stop set (0 <= ids < vocab; n = 0 restores
    cfg.eos_ids).  Ollama's `stop` option; bench.py --eos uses a synthetic set so that random-init
    weights finish chunks at natural, varied lengths (slot turnover). */
 int ms_set_eos_ids(ms_engine* e, const int32_t* ids, int32_t n);
-/* one scheduler iteration: admit + prefill, then a decode run of up to 64 chained greedy
-   steps with one host synchronisation (fewer when a chunk reaches num_predict, the
+/* one scheduler iteration: admit + prefill, then a decode run of up to 64 chained
+   steps (greedy, or sampled on the device when a chunk of the run samples) with one host synchronisation (fewer when a chunk reaches num_predict, the
    attention split grid changes, or admissible work waits for a slot); a chunk that meets
    EOS mid-run stops there.  Returns sequences still waiting or running (>= 0).
    MS_DECODE_RUN=1 in the environment restores one decode step per call. */
@@ -201,8 +227,10 @@ int ms_set_persist(ms_engine* e, int32_t on);
    engine's streams are idle) */
 #define MS_DBG_KPOOL 0          /* K cache [layer][page][kv_head][64][head_dim] fp16 */
 #define MS_DBG_VPOOL 1          /* V cache, same layout */
-#define MS_DBG_DECODE_LOGITS 2  /* the decode lm_head output (argmax partials {max, id} per 16 columns) */
+#define MS_DBG_DECODE_LOGITS 2  /* the decode lm_head output (argmax partials {max, id} per 16 columns;
+                                   after a sampling run: the scaled fp32 logits [rows][vocab]) */
 #define MS_DBG_DECODE_X 3       /* the decode residual [max_batch][hidden] fp32 */
+#define MS_DBG_PREFILL_LOGITS 4 /* the scaled fp32 logits [prompts][vocab] behind the latest prefill's first tokens */
 int ms_debug_read(ms_engine* e, int32_t which, int64_t offset, void* host, int64_t bytes);
 /* diagnostic: the persistent step's in-kernel timeline of its latest launch, [256][28][16]
    s_memrealtime ticks (100 MHz), recorded only under MS_PK_STAMPS=1 (tools/pk_stamps.py) */
@@ -338,6 +366,15 @@ int ms_op_rmsnorm(const void* x, const void* w, void* y, float* ssq, int32_t row
 int ms_op_argmax(const void* logits, int32_t rows, int32_t n, int32_t* ids, void* stream);
 /* ids[r] = the lowest id of the largest {max, id} partial of row r (MS_EPI_ARGMAX output) */
 int ms_op_argmax_partials(const void* partials, int32_t rows, int32_t tiles, int32_t* ids, void* stream);
+/* the row sampler (ms_sampling above) over device logits [rows][ldl] fp32, n <= 131072 columns:
+   params [rows]; win [rows][MS_SAMPLE_MAX_WINDOW] with win_len[r] <= 256 ids of row r's history,
+   oldest first (the penalty window is the last repeat_last_n of them); steps [rows]; ids [rows]
+   (-1: the row's largest non-NaN logit is not finite).  Optional, all three or none: the final
+   candidates cand_ids / cand_p [rows][MS_SAMPLE_MAX_TOPK] in (logit desc, id asc) order with
+   their probabilities, and their counts cand_n [rows].  Every pointer is a device pointer. */
+int ms_op_sample(const float* logits, int32_t rows, int32_t n, int64_t ldl, const ms_sampling* params,
+                 const int32_t* win, const int32_t* win_len, const int32_t* steps, int32_t* ids,
+                 int32_t* cand_ids, float* cand_p, int32_t* cand_n, void* stream);
 
 #ifdef __cplusplus
 }

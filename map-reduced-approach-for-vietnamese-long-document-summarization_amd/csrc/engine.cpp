@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -88,6 +89,9 @@ struct Seq {
   // teacher forcing (ms_submit_forced, parity tests): decode step j is fed forced[j-1]
   // instead of the sequence's own previous choice; `out` keeps the engine's choices
   std::vector<int32_t> forced;
+  // sampled decoding (ms_submit_sampled): sp.temperature > 0
+  bool sampled = false;
+  ms_sampling sp{};
   int32_t next_input() const { return forced.empty() ? out.back() : forced[out.size() - 1]; }
 };
 
@@ -314,7 +318,8 @@ struct ms_engine {
   // key: (batch rows, attention split grid, decode steps captured in the graph)
   // (graph, last use) -- least recently used graphs are destroyed beyond kMaxGraphs, so ragged
   // or admission-ramp workloads with many distinct (B, length bucket) keys stay bounded
-  std::map<std::tuple<int, int, int>, std::pair<hipGraphExec_t, uint64_t>> decode_graphs;
+  // (+ whether the run samples: a sampling run stores logits and ends in the sampling tail)
+  std::map<std::tuple<int, int, int, int>, std::pair<hipGraphExec_t, uint64_t>> decode_graphs;
   uint64_t graph_clock = 0;
   static constexpr size_t kMaxGraphs = 64;
   // chained decode steps per graph launch (MS_GRAPH_STEPS): 16 measured 12.12 -> 12.20
@@ -327,6 +332,15 @@ struct ms_engine {
   int32_t* ids_ring_d = nullptr;  // device ring of a decode run's ids (decode_advance)
   static constexpr int kMaxRun = 64;  // chained decode steps per host synchronisation
   int max_run = kMaxRun;              // MS_DECODE_RUN (1 = one step per ms_step)
+  // Sampled decoding (k_sample.hip): every slot's sampler state lives on the device -- its
+  // parameters, the repeat-penalty window ring and the per-request step counter -- written once
+  // at admission (the window seeded from the prompt's tail) and advanced only by the kernels, so
+  // nothing is uploaded per step and chained runs sample inside the captured graph.  A slot's
+  // state is (re)written when a sampling chunk takes it, or when a greedy chunk takes a slot a
+  // sampling chunk left (slot_sampled); untouched slots hold zeros = greedy.
+  SampleSlot* samp_d = nullptr;  // [max_batch]
+  SampleSlot* samp_h = nullptr;  // pinned staging, one entry per slot
+  std::vector<uint8_t> slot_sampled;
 
   template <class T>
   T* dalloc(size_t n, bool zero = false) {
@@ -965,6 +979,9 @@ int ms_create(const ms_config* cfg, ms_engine** out) {
       E.pk_ssq2 = E.dalloc<float>((size_t)256 * cfg->max_batch, true);
     }
     HIP_OK(hipHostMalloc((void**)&E.first_host, (size_t)cfg->max_batch * sizeof(int32_t), hipHostMallocDefault));
+    E.samp_d = E.dalloc<SampleSlot>(cfg->max_batch, true);
+    HIP_OK(hipHostMalloc((void**)&E.samp_h, (size_t)cfg->max_batch * sizeof(SampleSlot), hipHostMallocDefault));
+    E.slot_sampled.assign(cfg->max_batch, 0);
     if (const char* v = getenv("MS_DECODE_RUN")) E.max_run = std::max(1, std::min(atoi(v), (int)ms_engine::kMaxRun));
     if (const char* ng = getenv("MAPSUM_NO_GRAPHS")) E.use_graphs = !(ng[0] == '1');
     HIP_OK(hipDeviceSynchronize());
@@ -989,6 +1006,7 @@ int ms_destroy(ms_engine* e) {
   if (e->ids_host) (void)hipHostFree(e->ids_host);
   if (e->pk_err_h) (void)hipHostFree(e->pk_err_h);
   if (e->first_host) (void)hipHostFree(e->first_host);
+  if (e->samp_h) (void)hipHostFree(e->samp_h);
   if (e->bt_h) (void)hipHostFree(e->bt_h);
   for (auto& kv : e->decode_graphs) (void)hipGraphExecDestroy(kv.second.first);
   for (auto& pe : e->ev_pairs) {
@@ -1309,6 +1327,36 @@ int ms_submit(ms_engine* e, const int32_t* ids, int32_t n, int32_t num_predict, 
   });
 }
 
+static_assert(sizeof(ms_sampling) == sizeof(SampleParams) && offsetof(ms_sampling, seed) == offsetof(SampleParams, seed) &&
+                  offsetof(ms_sampling, repeat_last_n) == offsetof(SampleParams, repeat_last_n),
+              "ms_sampling is the kernels' SampleParams");
+
+int ms_submit_sampled(ms_engine* e, const int32_t* ids, int32_t n, int32_t num_predict, uint32_t flags,
+                      uint64_t tag, const ms_sampling* sp) {
+  if (!e) return MS_EINVAL;
+  if (!sp || !(sp->temperature > 0.f)) return ms_submit(e, ids, n, num_predict, flags, tag);
+  return guarded(e, [&]() -> int {
+    ms_engine& E = *e;
+    REQUIRE(sp->top_k >= 1 && sp->top_k <= MS_SAMPLE_MAX_TOPK, MS_EINVAL,
+            "sampling: top_k must be in [1, " + std::to_string(MS_SAMPLE_MAX_TOPK) + "], got " +
+                std::to_string(sp->top_k));
+    REQUIRE(sp->top_p > 0.f, MS_EINVAL, "sampling: top_p must be > 0");
+    REQUIRE(sp->min_p >= 0.f && sp->min_p < 1.f, MS_EINVAL, "sampling: min_p must be in [0, 1)");
+    REQUIRE(sp->repeat_penalty > 0.f && std::isfinite(sp->repeat_penalty), MS_EINVAL,
+            "sampling: repeat_penalty must be > 0");
+    REQUIRE(sp->repeat_last_n >= 0 && sp->repeat_last_n <= MS_SAMPLE_MAX_WINDOW, MS_EINVAL,
+            "sampling: repeat_last_n must be in [0, " + std::to_string(MS_SAMPLE_MAX_WINDOW) + "], got " +
+                std::to_string(sp->repeat_last_n));
+    REQUIRE(std::isfinite(sp->temperature), MS_EINVAL, "sampling: temperature must be finite");
+    REQUIRE(E.V <= kSampleMaxN, MS_EINVAL, "sampling: vocab above " + std::to_string(kSampleMaxN));
+    submit_seq(E, ids, n, num_predict, flags, tag, nullptr, 0);
+    Seq& s = *E.waiting.back();
+    s.sampled = true;
+    s.sp = *sp;
+    return MS_OK;
+  });
+}
+
 int ms_submit_forced(ms_engine* e, const int32_t* ids, int32_t n, const int32_t* forced, int32_t n_forced,
                      int32_t num_predict, uint32_t flags, uint64_t tag) {
   if (!e) return MS_EINVAL;
@@ -1390,6 +1438,23 @@ static void reserve(ms_engine& E, Seq& s, int tokens) {
                         hipMemcpyHostToDevice, E.stream));
 }
 
+// the sampler state of a newly admitted chunk's slot (prefill stream, before its first draw):
+// parameters, step 0 and the window ring seeded from the prompt's last <= 256 ids.  Greedy chunks
+// write nothing unless a sampling chunk used the slot before them.
+static void admit_sampling(ms_engine& E, Seq& s) {
+  if (!s.sampled && !E.slot_sampled[s.slot]) return;
+  SampleSlot& h = E.samp_h[s.slot];
+  std::memset(&h, 0, sizeof(h));
+  if (s.sampled) {
+    std::memcpy(&h.p, &s.sp, sizeof(h.p));
+    const int n = (int)s.prompt.size(), w = std::min(n, (int)kSampleMaxWindow);
+    for (int i = 0; i < w; ++i) h.ring[i] = s.prompt[n - w + i];
+    h.wcount = w;
+  }
+  HIP_OK(hipMemcpyAsync(E.samp_d + s.slot, &h, sizeof(h), hipMemcpyHostToDevice, E.stream));
+  E.slot_sampled[s.slot] = s.sampled ? 1 : 0;
+}
+
 // packed varlen prefill of `batch` (fresh sequences); writes K/V, returns first greedy ids.
 // If n_layers_run < L: stops after that many layers (probe mode, no logits).
 static void prefill(ms_engine& E, std::vector<Seq*>& batch, int n_layers_run, float* logits_all,
@@ -1468,8 +1533,21 @@ static void prefill(ms_engine& E, std::vector<Seq*>& batch, int n_layers_run, fl
     E.gemm_or_gemv(E.xb + (size_t)r0 * E.H, E.lm_head, E.logits + (size_t)r0 * E.V, rows, E.V, E.H, E.V,
                    MS_EPI_STORE_F32, true, K_LMHEAD, &rs);
   }
+  bool samp = false;
+  for (Seq* s : batch) samp = samp || s->sampled;
   E.prof_begin(K_MISC);
-  launch_argmax(E.logits, S, E.V, E.ids_out_d, E.stream);
+  if (samp) {  // step 0 of the sampling chunks (greedy rows: the same argmax), state advanced
+    SampleArgs sa{};
+    sa.logits = E.logits;
+    sa.ldl = E.V;
+    sa.n = E.V;
+    sa.slots = E.samp_d;
+    sa.row_slot = d + o_sslot;
+    sa.ids_out = E.ids_out_d;
+    launch_sample_rows(sa, S, E.stream);
+  } else {
+    launch_argmax(E.logits, S, E.V, E.ids_out_d, E.stream);
+  }
   E.prof_end(K_MISC);
   HIP_OK(hipGetLastError());
   // pinned landing buffer: a pageable destination would make this copy wait for the prefill
@@ -1550,7 +1628,46 @@ static void persist_layers(ms_engine& E, int B, const DecodeAttnArgs& da) {
 // with the step's layer-0 input in x / xb / ssq and leaves the NEXT step's there: the greedy
 // ids, the argument advance and the next embedding gather are one launch (decode_tail_kernel)
 // on the argmax-partials lm_head paths.
-static void decode_body(ms_engine& E, int B, int32_t* d, const DecodeAttnArgs& da) {
+// A sampling run's lm_head and tail: the regime's own kernel family and weight form with the
+// fp32 store epilogue and the deferred row scale into E.logits [B][V], then the fused sampling
+// tail.  GEMV / Q-GEMV row groups, the skinny GEMM, the K-quant skinny GEMM and the 128x128 tile
+// all have that epilogue; a shape none of them takes falls to gemm_or_gemv like the greedy body.
+static void decode_sampled_tail(ms_engine& E, int B, int32_t* d) {
+  const RowScale rs = E.cur_rs;
+  const int Bg = std::min(B, (int)ms_engine::kMaxGemvRows);
+  bool done = false;
+  if (E.large(B)) {
+    E.prof_begin(K_LMHEAD);
+    if (rs.tiles == 1 && E.qd(&E.lmq, B, E.V, E.H, 1, MS_GEMV_EPI_STORE_F32)) {
+      launch_qdgemm(E.xb, E.lmq.m, E.logits, B, E.V, E.H, 1, E.V, MS_GEMV_EPI_STORE_F32, E.stream, &rs);
+      done = true;
+    } else if (E.lm_gemm_min > 0 && E.cfg.max_batch >= E.lm_gemm_min && E.H % 64 == 0 &&
+               gemm_rs_tiles_ok(B, E.V, rs.tiles)) {
+      launch_gemm(E.xb, E.lm_head, E.logits, B, E.V, E.H, E.V, MS_EPI_STORE_F32, E.stream, &rs);
+      done = true;
+    } else if (rs.tiles == 1 && dgemm_supported(B, E.V, E.H, 1, MS_GEMV_EPI_STORE_F32, 1,
+                                                B <= 128 && E.V % 128 == 0 ? E.dwn_lm : 4)) {
+      launch_dgemm(E.xb, E.lm_head, E.logits, B, E.V, E.H, 1, E.V, MS_GEMV_EPI_STORE_F32, E.stream, &rs, 1,
+                   B <= 128 && E.V % 128 == 0 ? E.dwn_lm : 4);
+      done = true;
+    }
+    E.prof_end(K_LMHEAD);
+  } else if (gemv_supported(Bg, E.V, E.H, MS_GEMV_EPI_STORE_F32, rs.tiles) &&
+             (B <= ms_engine::kMaxGemvRows || (E.row_groups(B) && rs.tiles == 1))) {
+    GemvArgs ga{};
+    ga.rs = rs;
+    const QSlot* q = E.lmq.ready() && qgemv_supported(Bg, E.V, E.H, MS_GEMV_EPI_STORE_F32, rs.tiles) ? &E.lmq : nullptr;
+    E.proj(q, E.xb, E.lm_head, E.logits, B, E.V, E.H, E.V, MS_GEMV_EPI_STORE_F32, &ga, K_LMHEAD, sizeof(float));
+    done = true;
+  }
+  if (!done) E.gemm_or_gemv(E.xb, E.lm_head, E.logits, B, E.V, E.H, E.V, MS_EPI_STORE_F32, true, K_LMHEAD, &rs);
+  E.prof_begin(K_MISC);
+  launch_sample_tail(E.logits, E.samp_d, d, E.ids_out_d, E.ids_ring_d, B, E.V, E.embed, E.H, E.x,
+                     E.layers[0].attn_norm, E.xb, E.ssq, E.stream);
+  E.prof_end(K_MISC);
+}
+
+static void decode_body(ms_engine& E, int B, int32_t* d, const DecodeAttnArgs& da, bool samp = false) {
   const size_t o_pos = B, o_slot = 2 * (size_t)B;
   PrefillAttnArgs pa{};
   E.pending_split = 0;
@@ -1560,6 +1677,10 @@ static void decode_body(ms_engine& E, int B, int32_t* d, const DecodeAttnArgs& d
   } else {
     // every layer leaves xb = f16(x * the next gain) with its deferred scale in cur_rs
     for (int l = 0; l < E.L; ++l) E.run_layer(l, B, true, d + o_pos, d + o_slot, pa, da);
+  }
+  if (samp) {
+    decode_sampled_tail(E, B, d);
+    return;
   }
   const RowScale rs = E.cur_rs;
   if (E.large(B) && dgemm_supported(B, E.V, E.H, 1, MS_GEMV_EPI_ARGMAX, 1)) {
@@ -1612,6 +1733,9 @@ static void decode_run(ms_engine& E, std::vector<Seq*>& batch, int k, std::vecto
   for (Seq* s : batch) a.push_back(s->len);         // [B, 2B)  positions
   for (Seq* s : batch) a.push_back(s->slot);        // [2B, 3B) block-table rows
   for (Seq* s : batch) { a.push_back(s->len + 1); max_len = std::max(max_len, s->len + 1); }
+  // the run samples when one of its rows does (B <= 256: one block per row, like the fused tail)
+  bool samp = false;
+  for (Seq* s : batch) samp = samp || (s->sampled && !s->finish);
   a.push_back(0);                                   // [4B]     step of the run (ring row)
   a.push_back(0);                                   // [4B+1]   decode_tail's arrival ticket
   // the persistent step runs (captured or eagerly) exactly when persist_on holds for this run;
@@ -1652,14 +1776,14 @@ static void decode_run(ms_engine& E, std::vector<Seq*>& batch, int k, std::vecto
   da.max_len = ((max_len + k - 1 + 255) / 256) * 256;
   da.ppw = E.attn_ppw;
   auto graph = [&](int steps) {  // `steps` chained decode bodies in one graph
-    const auto key = std::make_tuple(B, da.max_len, steps);
+    const auto key = std::make_tuple(B, da.max_len, steps, samp ? 1 : 0);
     auto it = E.decode_graphs.find(key);
     if (it == E.decode_graphs.end()) {
       E.evict_graphs();
       hipGraph_t g = nullptr;
       hipGraphExec_t ex = nullptr;
       HIP_OK(hipStreamBeginCapture(E.stream, hipStreamCaptureModeRelaxed));
-      for (int i = 0; i < steps; ++i) decode_body(E, B, d, da);
+      for (int i = 0; i < steps; ++i) decode_body(E, B, d, da, samp);
       HIP_OK(hipStreamEndCapture(E.stream, &g));
       HIP_OK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
       HIP_OK(hipGraphDestroy(g));
@@ -1674,7 +1798,7 @@ static void decode_run(ms_engine& E, std::vector<Seq*>& batch, int k, std::vecto
     for (int j = 0; j + G <= k; j += G) HIP_OK(hipGraphLaunch(graph(G), E.stream));
     for (int j = 0; j < k % G; ++j) HIP_OK(hipGraphLaunch(graph(1), E.stream));
   } else {
-    for (int j = 0; j < k; ++j) decode_body(E, B, d, da);
+    for (int j = 0; j < k; ++j) decode_body(E, B, d, da, samp);
   }
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(E.ev_b, E.stream));
@@ -1726,6 +1850,7 @@ int ms_step(ms_engine* e) {
       const int need = (n + s.num_predict + kPage - 1) / kPage;
       if (need > (int)E.free_pages.size() || n > budget) break;
       reserve(E, s, n + s.num_predict);
+      admit_sampling(E, s);
       budget -= n;
       admitted.push_back(&s);
       E.running.push_back(std::move(E.waiting.front()));
@@ -1890,6 +2015,7 @@ int ms_debug_read(ms_engine* e, int32_t which, int64_t offset, void* host, int64
       case MS_DBG_VPOOL: base = E.vpool; cap = E.layer_kv_elems * E.L * sizeof(f16_t); break;
       case MS_DBG_DECODE_LOGITS: base = E.cd.logits; cap = (size_t)E.cfg.max_batch * E.V * sizeof(float); break;
       case MS_DBG_DECODE_X: base = E.cd.x; cap = (size_t)E.cfg.max_batch * E.H * sizeof(float); break;
+      case MS_DBG_PREFILL_LOGITS: base = E.cp.logits; cap = (size_t)E.cfg.max_batch * E.V * sizeof(float); break;
       default: REQUIRE(false, MS_EINVAL, "ms_debug_read: unknown buffer");
     }
     REQUIRE((size_t)offset + (size_t)bytes <= cap, MS_EINVAL, "ms_debug_read: range past the buffer");
@@ -2259,6 +2385,31 @@ int ms_op_argmax_partials(const void* partials, int32_t rows, int32_t tiles, int
   return op_guard([&] {
     REQUIRE(partials && ids && rows >= 1 && tiles >= 1, MS_EINVAL, "bad argmax_partials shape");
     launch_argmax_partials(partials, rows, tiles, ids, (hipStream_t)stream);
+  });
+}
+
+int ms_op_sample(const float* logits, int32_t rows, int32_t n, int64_t ldl, const ms_sampling* params,
+                 const int32_t* win, const int32_t* win_len, const int32_t* steps, int32_t* ids,
+                 int32_t* cand_ids, float* cand_p, int32_t* cand_n, void* stream) {
+  return op_guard([&] {
+    REQUIRE(logits && params && win && win_len && steps && ids && rows >= 1, MS_EINVAL, "bad sample operands");
+    REQUIRE(n >= 1 && n <= kSampleMaxN && ldl >= n, MS_EINVAL,
+            "bad sample shape (1 <= n <= " + std::to_string(kSampleMaxN) + ", ldl >= n)");
+    REQUIRE((cand_ids && cand_p && cand_n) || (!cand_ids && !cand_p && !cand_n), MS_EINVAL,
+            "sample: the candidate outputs come together");
+    SampleArgs a{};
+    a.logits = logits;
+    a.ldl = ldl;
+    a.n = n;
+    a.params = reinterpret_cast<const SampleParams*>(params);
+    a.win = win;
+    a.win_len = win_len;
+    a.steps = steps;
+    a.ids_out = ids;
+    a.cand_ids = cand_ids;
+    a.cand_p = cand_p;
+    a.cand_n = cand_n;
+    launch_sample_rows(a, rows, (hipStream_t)stream);
   });
 }
 

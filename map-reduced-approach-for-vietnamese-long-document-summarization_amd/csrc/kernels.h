@@ -99,6 +99,51 @@ void launch_rope_kv(f16_t* qkv, int T, int Hq, int Hk, const int32_t* tok_pos,
                     KVView kv, hipStream_t s, bool rope_q = true);
 void launch_argmax(const float* logits, int rows, int n, int32_t* out, hipStream_t s);
 
+// ---- sampled decoding (k_sample.hip; DESIGN.md "Sampler"): repeat penalty -> top-k -> top-p ->
+// min-p -> temperature -> one counter-based draw per row of stored fp32 logits
+constexpr int kSampleMaxTopK = 256, kSampleMaxWindow = 256;
+constexpr int kSampleMaxN = 131072;  // columns: the penalty window is a bitmap over them in LDS
+struct SampleParams {  // the layout of mapsum.h's ms_sampling
+  float temperature;   // <= 0: greedy (the argmax, every other field ignored)
+  int32_t top_k;
+  float top_p, min_p, repeat_penalty;
+  int32_t repeat_last_n;
+  uint64_t seed;
+};
+// one engine slot's sampler state: written at admission, then advanced only by the kernels
+struct SampleSlot {
+  SampleParams p;
+  int32_t wcount;  // ids appended so far; the newest is ring[(wcount - 1) & 255]
+  int32_t step;    // index of the next generated token (the draw's counter)
+  int32_t ring[kSampleMaxWindow];
+};
+struct SampleArgs {
+  const float* logits;  // [rows][ldl]
+  int64_t ldl;
+  int n;
+  // per-row arrays (slots == nullptr): window ids [rows][256] (the last win_len[r] <= 256 ids in
+  // order, oldest first), steps
+  const SampleParams* params;
+  const int32_t* win;
+  const int32_t* win_len;
+  const int32_t* steps;
+  // or the engine's state of slot row_slot[r], advanced after the draw
+  SampleSlot* slots;
+  const int32_t* row_slot;
+  int32_t* ids_out;
+  // optional (cand_n != nullptr): the final candidates [rows][256] in sorted order, their
+  // probabilities and counts
+  int32_t* cand_ids;
+  float* cand_p;
+  int32_t* cand_n;
+};
+void launch_sample_rows(const SampleArgs& a, int rows, hipStream_t s);
+// launch_decode_tail's counterpart of a sampling run: the ids from the stored, scaled logits
+// [B][V] by each row's slot state (slot = args[2B + b]; greedy rows: the argmax)
+void launch_sample_tail(const float* logits, SampleSlot* slots, int32_t* args, int32_t* ids_out, int32_t* ring,
+                        int B, int V, const f16_t* emb, int H, float* x, const f16_t* gamma, f16_t* xg, float* ssq,
+                        hipStream_t s);
+
 // out (epi) A[M][K] . W[N][K]^T, MFMA 16x16x32 fp16, K % 64 == 0; rs (<= kGemmRsTiles tiles of
 // statistics, or null): the deferred RMSNorm scale of the output rows (epilogues 0, 2, 3).
 // gr (epilogue 1, the residual add of O / down): the GEMM also writes the next normalised

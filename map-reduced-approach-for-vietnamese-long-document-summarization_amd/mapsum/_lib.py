@@ -26,7 +26,8 @@ GEMM_DEFAULT = 4
 MS_GGML_Q4_K, MS_GGML_Q6_K = 12, 14
 # kernel classes of ms_stats.kernel_ms
 K_GEMM, K_ATTN_PREFILL, K_GEMV, K_ATTN_DECODE, K_LMHEAD, K_MISC, K_PERSIST = range(7)
-MS_DBG_KPOOL, MS_DBG_VPOOL, MS_DBG_DECODE_LOGITS, MS_DBG_DECODE_X = range(4)
+MS_DBG_KPOOL, MS_DBG_VPOOL, MS_DBG_DECODE_LOGITS, MS_DBG_DECODE_X, MS_DBG_PREFILL_LOGITS = range(5)
+MS_SAMPLE_MAX_TOPK, MS_SAMPLE_MAX_WINDOW = 256, 256
 
 EXPORTED = (
     "ms_create", "ms_destroy", "ms_last_error", "ms_load_weight", "ms_init_synthetic",
@@ -39,6 +40,7 @@ EXPORTED = (
     "ms_forward_packed", "ms_submit_forced", "ms_set_eos_ids", "ms_op_gemv_strided",
     "ms_op_gemv_resid", "ms_op_set_row_scale", "ms_op_gemm_resid", "ms_gemm_resid_tiles",
     "ms_trace_push", "ms_trace_pop", "ms_debug_a2_stamps", "ms_set_persist", "ms_debug_read", "ms_debug_pk_stamps",
+    "ms_submit_sampled", "ms_op_sample",
 )
 
 
@@ -53,6 +55,12 @@ class MsConfig(C.Structure):
                 ("device", C.c_int32), ("max_batch", C.c_int32), ("max_ctx", C.c_int32),
                 ("max_prefill_tokens", C.c_int32), ("n_pages", C.c_int32), ("n_eos", C.c_int32),
                 ("eos_ids", C.c_int32 * 8)]
+
+
+class MsSampling(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float),
+                ("min_p", C.c_float), ("repeat_penalty", C.c_float), ("repeat_last_n", C.c_int32),
+                ("seed", C.c_uint64)]
 
 
 class MsResult(C.Structure):
@@ -104,6 +112,8 @@ def load_at(path: str, ab: bool = True) -> C.CDLL:
         "ms_op_qgemv_split": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, vp]),
         "ms_op_qdgemm": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
         "ms_submit": (i32, [vp, pi32, i32, i32, u32, u64]),
+        "ms_submit_sampled": (i32, [vp, pi32, i32, i32, u32, u64, C.POINTER(MsSampling)]),
+        "ms_op_sample": (i32, [vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ms_step": (i32, [vp]),
         "ms_poll": (i32, [vp, C.POINTER(MsResult), i32]),
         "ms_pending": (i32, [vp]),

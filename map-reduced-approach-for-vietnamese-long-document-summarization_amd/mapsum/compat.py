@@ -24,6 +24,7 @@ import concurrent.futures
 import os
 import threading
 
+from .engine import Sampling
 from .postprocess import CLEANERS
 from .template import render_llama32
 
@@ -48,7 +49,7 @@ class MapBackend:
         self.template = template
         self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="mapsum")
         self._lock = threading.Lock()
-        self._queue = []          # (ids, num_predict, future) waiting for the driver
+        self._queue = []          # (tag, ids, num_predict, sampling) waiting for the driver
         self._inflight = {}       # tag -> future
         self._driver = None
         self._tag = _ASYNC_TAG0
@@ -58,33 +59,39 @@ class MapBackend:
         return self.tok.encode(self.template(prompt, add_bos=False), add_bos=True)
 
     # -- synchronous path (one chunk, or a list of chunks) ----------------------
-    def generate_ids(self, id_lists, num_predict: int) -> list:
-        res = self._pool.submit(self.engine.generate, id_lists, num_predict, False, self.retries).result()
+    def generate_ids(self, id_lists, num_predict: int, sampling=None) -> list:
+        args = (id_lists, num_predict, False, self.retries)
+        if sampling is not None:  # None: the call a greedy caller always made
+            args += (sampling,)
+        res = self._pool.submit(self.engine.generate, *args).result()
         for r in res:
             if r.finish == "error":  # deterministic: a re-run would fail the same way
                 raise RuntimeError("mapsum: chunk failed (no finite logit)")
         return res
 
-    def generate(self, prompts, num_predict: int) -> list:
+    def generate(self, prompts, num_predict: int, sampling=None) -> list:
+        """``sampling``: None (greedy), one mapsum.engine.Sampling, or one per prompt."""
         ids = [self.encode_prompt(p) for p in prompts]
-        res = self.generate_ids(ids, num_predict)
+        res = self.generate_ids(ids, num_predict, sampling)
         return [self.tok.decode(r.ids) for r in res]
 
     # -- asynchronous path: continuous batching across concurrent callers ---------
-    async def agenerate(self, prompt: str, num_predict: int) -> str:
-        return (await self.agenerate_full(prompt, num_predict))[0]
+    async def agenerate(self, prompt: str, num_predict: int, sampling=None) -> str:
+        return (await self.agenerate_full(prompt, num_predict, sampling))[0]
 
-    async def agenerate_full(self, prompt: str, num_predict: int):
+    async def agenerate_full(self, prompt: str, num_predict: int, sampling=None):
         """(text, finish) with finish in {"eos", "length"} -- Ollama's done_reason
-        "stop" / "length"."""
+        "stop" / "length".  A seedless ``sampling`` gets its seed here, so a re-queue keeps it."""
         loop = asyncio.get_running_loop()
         fut = loop.create_future()
         ids = self.encode_prompt(prompt)
+        if sampling is not None:
+            sampling = None if sampling.greedy else sampling.validate().with_seed()
         with self._lock:
             self._tag += 1
             tag = self._tag
-        self._queue.append((tag, ids, num_predict))
-        self._inflight[tag] = (fut, ids, num_predict, self.retries)
+        self._queue.append((tag, ids, num_predict, sampling))
+        self._inflight[tag] = (fut, ids, num_predict, self.retries, sampling)
         if self._driver is None or self._driver.done():
             self._driver = asyncio.ensure_future(self._drive())
         r = await fut
@@ -94,9 +101,12 @@ class MapBackend:
         """Engine thread: submit the new requests (a request the engine refuses fails
         alone), run one scheduler iteration, return this backend's finished results."""
         refused = []
-        for tag, ids, n in new:
+        for tag, ids, n, sampling in new:
             try:
-                self.engine.submit(ids, n, tag=tag)
+                if sampling is None:
+                    self.engine.submit(ids, n, tag=tag)
+                else:
+                    self.engine.submit(ids, n, tag=tag, sampling=sampling)
             except Exception as e:  # noqa: BLE001 -- e.g. ENOSPC: prompt + num_predict > max_ctx
                 refused.append((tag, e))
         self.engine.step()
@@ -117,7 +127,7 @@ class MapBackend:
                     ent = self._inflight.pop(r.tag, None)
                     if ent is None:
                         continue
-                    fut, ids, n, retries = ent
+                    fut, ids, n, retries, sampling = ent
                     if fut.done():
                         continue
                     if r.finish != "error":
@@ -126,8 +136,8 @@ class MapBackend:
                         with self._lock:
                             self._tag += 1
                             tag = self._tag
-                        self._queue.append((tag, ids, n))
-                        self._inflight[tag] = (fut, ids, n, retries - 1)
+                        self._queue.append((tag, ids, n, sampling))
+                        self._inflight[tag] = (fut, ids, n, retries - 1, sampling)
                     else:
                         fut.set_exception(RuntimeError("mapsum: chunk failed (no finite logit)"))
         except Exception as e:  # the engine itself failed: every waiter fails loudly
@@ -213,6 +223,17 @@ def _default_factory(model_name: str) -> MapBackend:
     return gguf_backend(m.gguf, params=m.params)
 
 
+def default_sampling() -> Sampling | None:
+    """The decoding of a call that names no options: greedy, or Ollama's defaults (what the
+    reference's runner gets from Ollama) with MAPSUM_SAMPLING=ollama in the environment."""
+    v = os.environ.get("MAPSUM_SAMPLING", "").strip().lower()
+    if v in ("", "greedy", "0"):
+        return None
+    if v == "ollama":
+        return Sampling.ollama_defaults()
+    raise ValueError(f"MAPSUM_SAMPLING must be 'ollama' or 'greedy', got {v!r}")
+
+
 def get_backend(model_name: str) -> MapBackend:
     if model_name not in _BACKENDS:
         _BACKENDS[model_name] = (_FACTORY or _default_factory)(model_name)
@@ -226,29 +247,45 @@ class OllamaLLM(_Base):
     model_name: str = "llama3.2:3b"
     max_new_tokens: int = 2048
     clean: str = "pipeline"  # 'pipeline' | 'hierarchical' | 'none' (which runner's cleaner)
+    options: dict | None = None  # Ollama's sampling options (temperature, top_k, ..., seed)
 
     def __init__(self, ollama_url: str = "http://localhost:11434", model_name: str = "llama3.2:3b",
-                 max_new_tokens: int = 2048, clean: str = "pipeline", **kwargs):
+                 max_new_tokens: int = 2048, clean: str = "pipeline", *, options: dict | None = None,
+                 **kwargs):
         if _HAVE_LC:
             super().__init__(ollama_url=ollama_url, model_name=model_name,
-                             max_new_tokens=max_new_tokens, clean=clean, **kwargs)
+                             max_new_tokens=max_new_tokens, clean=clean, options=options, **kwargs)
         else:
+            self.options = options
             self.ollama_url = ollama_url  # kept for signature parity; no HTTP is made
             self.model_name = model_name
             self.max_new_tokens = max_new_tokens
             self.clean = clean
         if clean not in CLEANERS:
             raise ValueError(f"clean must be one of {sorted(CLEANERS)}")
+        self.sampling  # bad options fail here, not at the first call
+
+    @property
+    def sampling(self) -> Sampling | None:
+        """The decoding of this LLM's calls: its ``options`` over the process default
+        (``default_sampling``); None = greedy.  Without a ``seed`` option every call draws a
+        fresh 64-bit seed, as Ollama does."""
+        s = Sampling.from_options(self.options, default_sampling())
+        return None if s is None or s.greedy else s.validate()
 
     # ---- the reference surface --------------------------------------------------
     def _call(self, prompt: str, stop=None, run_manager=None, **kwargs) -> str:
         b = get_backend(self.model_name)
-        raw = b.generate([prompt], self.max_new_tokens)[0]
+        s = self.sampling
+        raw = (b.generate([prompt], self.max_new_tokens) if s is None
+               else b.generate([prompt], self.max_new_tokens, s))[0]
         return CLEANERS[self.clean](raw)
 
     async def _acall(self, prompt: str, stop=None, run_manager=None, **kwargs) -> str:
         b = get_backend(self.model_name)
-        raw = await b.agenerate(prompt, self.max_new_tokens)
+        s = self.sampling
+        raw = await (b.agenerate(prompt, self.max_new_tokens) if s is None
+                     else b.agenerate(prompt, self.max_new_tokens, s))
         return CLEANERS[self.clean](raw)
 
     @property
@@ -274,7 +311,9 @@ class OllamaLLM(_Base):
         def batch(self, inputs, config=None, **kwargs) -> list:
             """All prompts in one continuous batch (what the Send fan-out should have been)."""
             b = get_backend(self.model_name)
-            raw = b.generate([_as_text(i) for i in inputs], self.max_new_tokens)
+            s = self.sampling
+            raw = (b.generate([_as_text(i) for i in inputs], self.max_new_tokens) if s is None
+                   else b.generate([_as_text(i) for i in inputs], self.max_new_tokens, s))
             return [CLEANERS[self.clean](r) for r in raw]
 
 

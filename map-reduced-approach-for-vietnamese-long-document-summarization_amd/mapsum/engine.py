@@ -10,7 +10,8 @@ convenience the bench and the adapter use.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+import math
+from dataclasses import dataclass, replace
 
 import numpy as np
 
@@ -24,6 +25,104 @@ class Result:
     ids: list
     finish: str  # "eos" | "length" | "error"
     n_prompt: int
+
+
+# Ollama's option names that select the decoding (everything else in `options` is ignored here)
+SAMPLING_OPTIONS = ("temperature", "top_k", "top_p", "min_p", "repeat_penalty", "repeat_last_n", "seed")
+
+
+@dataclass(frozen=True)
+class Sampling:
+    """Decoding options of one request (libmapsum's ms_sampling; DESIGN.md "Sampler").
+
+    ``temperature <= 0`` is greedy and every other field is then ignored.  The defaults of the
+    non-temperature fields are Ollama's, so ``Sampling(temperature=0.8)`` is what Ollama does with
+    ``{"temperature": 0.8}``.  ``seed=None`` means "draw a fresh 64-bit seed for this call", as
+    Ollama does when the request carries none (see ``with_seed``)."""
+    temperature: float = 0.0
+    top_k: int = 40
+    top_p: float = 0.9
+    min_p: float = 0.0
+    repeat_penalty: float = 1.1
+    repeat_last_n: int = 64
+    seed: int | None = None
+
+    @classmethod
+    def ollama_defaults(cls, seed: int | None = None) -> "Sampling":
+        """What Ollama samples with when a request sends only num_predict, as the reference's
+        OllamaLLM._call does (run_full_evaluation_pipeline.py:81-88)."""
+        return cls(0.8, 40, 0.9, 0.0, 1.1, 64, seed)
+
+    @property
+    def greedy(self) -> bool:
+        return not self.temperature > 0
+
+    def validate(self) -> "Sampling":
+        """The engine's limits (ms_submit_sampled), raised as ValueError naming the field."""
+        if self.greedy:
+            return self
+        if not math.isfinite(self.temperature):
+            raise ValueError("sampling: temperature must be finite")
+        if not 1 <= self.top_k <= L.MS_SAMPLE_MAX_TOPK:
+            raise ValueError(f"sampling: top_k must be in [1, {L.MS_SAMPLE_MAX_TOPK}], got {self.top_k}")
+        if not self.top_p > 0:
+            raise ValueError("sampling: top_p must be > 0")
+        if not 0 <= self.min_p < 1:
+            raise ValueError("sampling: min_p must be in [0, 1)")
+        if not (self.repeat_penalty > 0 and math.isfinite(self.repeat_penalty)):
+            raise ValueError("sampling: repeat_penalty must be > 0")
+        if not 0 <= self.repeat_last_n <= L.MS_SAMPLE_MAX_WINDOW:
+            raise ValueError(f"sampling: repeat_last_n must be in [0, {L.MS_SAMPLE_MAX_WINDOW}], "
+                             f"got {self.repeat_last_n}")
+        if self.seed is not None and not 0 <= self.seed < 1 << 64:
+            raise ValueError("sampling: seed must be in [0, 2^64)")
+        return self
+
+    @classmethod
+    def from_options(cls, options, default: "Sampling | None" = None) -> "Sampling | None":
+        """An Ollama ``options`` object -> Sampling.  Options that name none of
+        SAMPLING_OPTIONS give ``default`` (None = greedy); the fields present override
+        ``default`` or, without one, Ollama's defaults.  Wrong types raise ValueError."""
+        opts = {k: options[k] for k in SAMPLING_OPTIONS if options and options.get(k) is not None}
+        if not opts:
+            return default
+        base = default if default is not None else cls.ollama_defaults()
+        kw = {}
+        for k, v in opts.items():
+            want = int if k in ("top_k", "repeat_last_n", "seed") else float
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or (want is int and int(v) != v):
+                raise ValueError(f"sampling: {k} must be {'an integer' if want is int else 'a number'}")
+            kw[k] = want(v)
+        if "seed" in kw:
+            kw["seed"] &= (1 << 64) - 1  # Ollama's seed is a signed int
+        return replace(base, **kw).validate()
+
+    def with_seed(self) -> "Sampling":
+        """This sampling with a concrete seed: its own, or a fresh 64-bit one per call."""
+        if self.greedy or self.seed is not None:
+            return self
+        import secrets
+        return replace(self, seed=secrets.randbits(64))
+
+    def key(self) -> str:
+        """Canonical text of a non-greedy call's options (the journal key, mapsum.resume)."""
+        return (f"T={self.temperature!r};k={self.top_k};p={self.top_p!r};m={self.min_p!r};"
+                f"rp={self.repeat_penalty!r};n={self.repeat_last_n};seed={'fresh' if self.seed is None else self.seed}")
+
+    def to_c(self) -> "L.MsSampling":
+        s = self.with_seed()
+        return L.MsSampling(s.temperature, s.top_k, s.top_p, s.min_p, s.repeat_penalty, s.repeat_last_n,
+                            s.seed or 0)
+
+
+def _per_prompt(sampling, n: int) -> list:
+    """``sampling`` as one value per prompt: None, one Sampling for all, or a sequence of n."""
+    if sampling is None or isinstance(sampling, Sampling):
+        return [sampling] * n
+    out = list(sampling)
+    if len(out) != n:
+        raise ValueError(f"sampling: {len(out)} values for {n} prompts")
+    return out
 
 
 _FINISH = {L.MS_FINISH_EOS: "eos", L.MS_FINISH_LENGTH: "length", L.MS_FINISH_ERROR: "error"}
@@ -57,7 +156,14 @@ class RequestQueue:
         mine = [t for t in self._mailbox if pred(t)]
         return [self._mailbox.pop(t) for t in mine]
 
-    def generate(self, prompts, num_predict: int, ignore_eos: bool = False, retries: int = 0) -> list:
+    def _submit(self, ids, num_predict, ignore_eos, sampling):
+        # the keyword only when there is something to say: greedy calls reach submit() unchanged
+        if sampling is None or sampling.greedy:
+            return self.submit(ids, num_predict, ignore_eos)
+        return self.submit(ids, num_predict, ignore_eos, sampling=sampling)
+
+    def generate(self, prompts, num_predict: int, ignore_eos: bool = False, retries: int = 0,
+                 sampling=None) -> list:
         """Run every prompt (list of id lists) to completion; results in input order.
 
         A chunk that finishes with MS_FINISH_ERROR (no finite logit: SURVEY.md §5 failure
@@ -65,8 +171,12 @@ class RequestQueue:
         deterministic and batch-invariant, so re-running such a chunk recomputes the same
         non-finite logits: by default it is reported at once.  ``retries`` > 0 re-queues it
         that many times, a guard against transient device faults only.  The reference has
-        no retry at all (run_full_evaluation_pipeline.py:627-638)."""
-        tags = [self.submit(p, num_predict, ignore_eos) for p in prompts]
+        no retry at all (run_full_evaluation_pipeline.py:627-638).
+
+        ``sampling``: None (greedy), one ``Sampling`` for every prompt, or one per prompt.  A
+        seedless Sampling gets its fresh seed here, once, so a re-queued chunk keeps its seed."""
+        samp = [None if s is None else s.with_seed() for s in _per_prompt(sampling, len(prompts))]
+        tags = [self._submit(p, num_predict, ignore_eos, s) for p, s in zip(prompts, samp)]
         order = {t: i for i, t in enumerate(tags)}
         left = {t: retries for t in tags}
         out = [None] * len(tags)
@@ -78,7 +188,7 @@ class RequestQueue:
                 waiting.discard(t)
                 i = order.pop(t)
                 if r.finish == "error" and left[t] > 0:
-                    nt = self.submit(prompts[i], num_predict, ignore_eos)
+                    nt = self._submit(prompts[i], num_predict, ignore_eos, samp[i])
                     order[nt], left[nt] = i, left[t] - 1
                     waiting.add(nt)
                     pending += 1
@@ -182,12 +292,19 @@ class Engine(RequestQueue):
                                           a.size), "ms_set_eos_ids")
 
     # ------------------------------------------------------------ request path
-    def submit(self, ids, num_predict: int, ignore_eos: bool = False, tag: int | None = None) -> int:
+    def submit(self, ids, num_predict: int, ignore_eos: bool = False, tag: int | None = None,
+               sampling: Sampling | None = None) -> int:
         a = np.ascontiguousarray(ids, dtype=np.int32)
         if tag is None:
             tag = self._next_tag
             self._next_tag += 1
         flags = L.MS_FLAG_IGNORE_EOS if ignore_eos else 0
+        if sampling is not None and not sampling.greedy:
+            sp = sampling.to_c()
+            self._chk(self.lib.ms_submit_sampled(self.h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
+                                                 int(num_predict), flags, int(tag), C.byref(sp)),
+                      "ms_submit_sampled")
+            return tag
         self._chk(self.lib.ms_submit(self.h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
                                      int(num_predict), flags, int(tag)), "ms_submit")
         return tag

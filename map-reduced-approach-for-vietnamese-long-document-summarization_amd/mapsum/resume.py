@@ -13,7 +13,8 @@ phase re-issues only the calls that had not finished.  ``JournaledLLM`` wraps th
 prompts return their stored text without touching the engine, the rest go through the
 wrapped LLM as one batch exactly as before.  Greedy decoding is deterministic and
 batch-invariant, so a resumed run returns the strings an uninterrupted run
-would have returned.
+would have returned; so is sampled decoding with a fixed seed, whose options and seed are
+part of the key.
 
 The journal is append-only; a torn last line (a crash mid-write) is ignored on load.
 """
@@ -25,9 +26,11 @@ import json
 import os
 
 
-def call_key(model: str, num_predict: int, doc_id: str, prompt: str) -> str:
+def call_key(model: str, num_predict: int, doc_id: str, prompt: str, sampling: str = "") -> str:
+    """``sampling``: the canonical options text of a non-greedy call (Sampling.key(), seed
+    included); empty for a greedy call, whose key is what it always was."""
     h = hashlib.sha256()
-    for part in (model, str(int(num_predict)), doc_id, prompt):
+    for part in (model, str(int(num_predict)), doc_id, prompt) + ((sampling,) if sampling else ()):
         b = part.encode("utf-8")
         h.update(len(b).to_bytes(8, "little"))
         h.update(b)
@@ -111,7 +114,11 @@ class JournaledLLM:
         self.misses = 0
 
     def _key(self, prompt: str) -> str:
-        return call_key(self.model, self.num_predict, self.doc_id, prompt)
+        # a sampled call's text depends on its options and seed (compat.OllamaLLM.sampling); a
+        # seedless one draws a fresh seed per call, and its journaled text stands for the call
+        s = getattr(self.llm, "sampling", None)
+        return call_key(self.model, self.num_predict, self.doc_id, prompt,
+                        "" if s is None or s.greedy else s.key())
 
     def get_num_tokens(self, text: str) -> int:
         return self.llm.get_num_tokens(text)

@@ -12,6 +12,11 @@ Requests from concurrent clients are batched: every request thread hands its pro
 one asyncio loop that drives ``MapBackend.agenerate``, so requests that arrive together
 share engine steps.  Errors are HTTP 500 with {"error": msg}, which the reference turns
 into an exception through ``raise_for_status`` (:91).
+
+``options.temperature / top_k / top_p / min_p / repeat_penalty / repeat_last_n / seed`` select
+sampled decoding (mapsum.engine.Sampling); a request that names none of them is greedy unless
+the shim was started with ``ollama_defaults=True`` (then: Ollama's defaults, a fresh seed per
+request).  A value outside the engine's limits is HTTP 400 with the engine's message.
 """
 from __future__ import annotations
 
@@ -21,13 +26,17 @@ import threading
 import time
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 
+from .engine import Sampling
+
 DEFAULT_NUM_PREDICT = 128  # EXT Ollama's default when options.num_predict is absent
 
 
 class OllamaShim:
-    def __init__(self, backends: dict, host: str = "127.0.0.1", port: int = 11434):
+    def __init__(self, backends: dict, host: str = "127.0.0.1", port: int = 11434,
+                 ollama_defaults: bool = False):
         """backends: model name -> mapsum.compat.MapBackend."""
         self.backends = backends
+        self.ollama_defaults = ollama_defaults
         self.loop = asyncio.new_event_loop()
         self._loop_thread = threading.Thread(target=self.loop.run_forever, daemon=True)
         shim = self
@@ -81,12 +90,23 @@ class OllamaShim:
         prompt = req.get("prompt")
         if not isinstance(prompt, str):
             return 400, {"error": "prompt must be a string"}
-        n = int((req.get("options") or {}).get("num_predict", DEFAULT_NUM_PREDICT))
+        opts = req.get("options") or {}
+        if not isinstance(opts, dict):
+            return 400, {"error": "options must be an object"}
+        n = int(opts.get("num_predict", DEFAULT_NUM_PREDICT))
+        try:
+            sampling = Sampling.from_options(opts, Sampling.ollama_defaults() if self.ollama_defaults else None)
+        except ValueError as e:
+            return 400, {"error": str(e)}
         t0 = time.perf_counter()
         try:
-            fut = asyncio.run_coroutine_threadsafe(be.agenerate_full(prompt, n), self.loop)
+            call = (be.agenerate_full(prompt, n) if sampling is None or sampling.greedy
+                    else be.agenerate_full(prompt, n, sampling))
+            fut = asyncio.run_coroutine_threadsafe(call, self.loop)
             text, finish = fut.result()
         except Exception as e:  # noqa: BLE001 -- reported to the client as Ollama does
+            if "(-22)" in str(e) and "sampling:" in str(e):  # the engine refused an option (MS_EINVAL)
+                return 400, {"error": str(e)}
             return 500, {"error": str(e)}
         dt = time.perf_counter() - t0
         return 200, {"model": model, "created_at": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()),
