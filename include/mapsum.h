@@ -92,7 +92,12 @@ typedef struct ms_config {
                                    >= 192 + the fp16-rows K-quant GEMM form;
                                    K-quant: 1-16 residual-fused Q-GEMV, 17-64
                                    split Q-GEMV + residual_rmsnorm, >= 65 the
-                                   K-quant skinny GEMM, lm_head tile from 96); results
+                                   K-quant skinny GEMM, lm_head tile from 96;
+                                   Q8_0: 1-16 residual-fused Q-GEMV, 17-64 split
+                                   Q-GEMV + residual_rmsnorm in row groups of
+                                   <= 64 (the exact d*q weights), >= 65 the fp16
+                                   copies on the skinny GEMM, lm_head tile from
+                                   96); results
                                    are batch-invariant inside one engine, not
                                    across these boundaries */
   int32_t max_ctx;              /* prompt + generated tokens per sequence     */
@@ -146,16 +151,21 @@ int ms_load_weight(ms_engine* e, int32_t tensor, int32_t layer, const uint16_t* 
 /* device-side counter-based N(0,std)-like init; restated in oracle/synth.py */
 int ms_init_synthetic(ms_engine* e, uint64_t seed, float std, float norm_jitter);
 
-/* ggml K-quant weights (Q4_K_M files: BASELINE.json config 5).  `blocks` are the tensor's
- * rows as raw ggml blocks (Q4_K = 144 B, Q6_K = 210 B per 256 weights).  The engine keeps
- * f16(dequant) for prefill and the blocks for the dequant-fused decode GEMV.  RMSNorm
- * weights stay fp16 (ms_load_weight). */
+/* ggml quantised weights: the K-quants (Q4_K_M files: BASELINE.json config 5) and Q8_0
+ * (llama3.2:3b-instruct-q8_0).  `blocks` are the tensor's rows as raw ggml blocks (Q4_K =
+ * 144 B, Q6_K = 210 B per 256 weights; Q8_0 = 34 B per 32 weights, so rows * (cols / 32) * 34
+ * bytes).  The engine keeps f16(dequant) for prefill and the blocks for the dequant-fused
+ * decode GEMV.  RMSNorm weights stay fp16 (ms_load_weight).  An engine's quantised matrices
+ * are all Q8_0 or all K-quant: the other family is refused with MS_EINVAL. */
+#define MS_GGML_Q8_0 8
 #define MS_GGML_Q4_K 12
 #define MS_GGML_Q6_K 14
 int ms_load_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t ggml_type,
                      const void* host_blocks, int64_t n_bytes);
 /* random Q4_K/Q6_K blocks with the Q4_K_M per-tensor type mix (bench) */
 int ms_init_synthetic_q(ms_engine* e, uint64_t seed, float scale, float norm_jitter);
+/* random Q8_0 blocks for every matrix, dequantised weights of std ~ scale (bench) */
+int ms_init_synthetic_q8_0(ms_engine* e, uint64_t seed, float scale, float norm_jitter);
 
 /* ---- weight broadcast (one process per GPU: rank 0 loads, the others receive over RCCL) -- */
 /* every device weight buffer in a fixed order (fp16 matrices and norms, then K-quant
@@ -283,9 +293,11 @@ int ms_gemm_resid_tiles(int32_t M, int32_t N);
    3 = 256x256 on 4 waves, 4 = 3 for the stored epilogues and 2 for the residual one; every
    variant gives the same bits) */
 int ms_set_gemm_variant(int32_t variant);
-/* tuning/test hook: the K-quant GEMVs that have a grid-stride two-stage form (the Q6_K lm_head
-   argmax, the Q4_K gate/up SwiGLU) take it (1, the default) or run one-tile blocks (0); the
-   two give bit-identical outputs */
+/* tuning/test hook: the quantised GEMVs that have a grid-stride two-stage form (the Q6_K and the
+   Q8_0 lm_head argmax, the Q4_K gate/up SwiGLU) all take it (1) or all run one-tile blocks (0);
+   the two give bit-identical outputs.  The library starts with the two K-quant forms on and the
+   Q8_0 one off (it measured slower); MS_QGEMV_GS is the mask (bit 0 Q6_K
+   lm_head, 1 Q4_K gate/up, 2 Q8_0 lm_head) */
 int ms_set_qgemv_gs(int32_t on);
 /* tuning/test hook: decode attention's split combine on the XCD-matched grid (1, default) or the
    (B, Hq) grid (0), and the v2 prologue form (0 default, 3 a dedicated prologue wave); every
@@ -337,9 +349,11 @@ int ms_op_gemv_split(const void* X, const void* W, float* slabs, int32_t M, int3
    normalised projection that follows: y fp16 = f16(x * w * 2^-4), ssq[r] = sum of x[r]^2 (one tile) */
 int ms_op_residual_rmsnorm(float* x, const float* slabs, int32_t S, const void* w, void* y, float* ssq,
                            int32_t rows, int32_t hidden, void* stream);
-/* K-quant ops: raw ggml blocks -> fp32 (bit-exact restatement of llama.cpp's
-   dequantize_row_q4_K/q6_K); raw rows -> fp16 rows + packed rows (Q6_K repacked to 224 B);
-   dequant-fused GEMV over packed rows (same epilogues as ms_op_gemv) */
+/* quantised-weight ops (Q4_K, Q6_K, Q8_0): raw ggml blocks -> fp32 (bit-exact restatement of
+   llama.cpp's dequantize_row_q4_K/q6_K/q8_0; n_blocks counts 256-weight units, for Q8_0 8 ggml
+   blocks = 272 B each); raw rows -> fp16 rows + packed rows (Q6_K repacked to 224 B, Q8_0 to
+   272 B units: 8 scales, then the regrouped quants); dequant-fused GEMV over packed rows (same
+   epilogues as ms_op_gemv) */
 int ms_op_dequant(int32_t ggml_type, const void* blocks, int64_t n_blocks, float* out, void* stream);
 int ms_op_quant_rows(int32_t ggml_type, const void* blocks, int32_t rows, int32_t K, void* f16_out,
                      void* packed_out, void* stream);
@@ -353,7 +367,7 @@ int ms_op_qgemv_split(const void* X, int32_t ggml_type, const void* packed_rows,
    dequantised in registers to its fp16-copy value f16(ggml dequant); epilogues MS_EPI_STORE_F32
    (S > 1: split-K slabs [S][M][N]), MS_EPI_SWIGLU, MS_EPI_ARGMAX; N % 64 == 0, K % (256 S) == 0
    with K / (256 S) even or a multiple of 3 (the engine's K-quant decode projections in engines
-   of >= 65 slots) */
+   of >= 65 slots).  Q4_K, Q6_K or F16 (1) rows: Q8_0 has no form here (MS_EINVAL) */
 int ms_op_qdgemm(const void* X, int32_t ggml_type, const void* packed_rows, void* out, int32_t M,
                  int32_t N, int32_t K, int32_t S, int32_t ldo, int32_t epilogue, void* stream);
 /* the input of a normalised projection: y fp16 [rows][hidden] = f16(x * w * 2^-4) and ssq[r] = sum

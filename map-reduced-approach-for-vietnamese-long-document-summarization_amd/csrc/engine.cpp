@@ -74,6 +74,10 @@ struct MsError : std::runtime_error {
     if (!(cond)) throw MsError((code), (msg));        \
   } while (0)
 
+const char* qtype_name(int type) {
+  return type == MS_QT_Q8_0 ? "Q8_0 (8)" : type == MS_QT_Q4_K ? "Q4_K (12)" : type == MS_QT_Q6_K ? "Q6_K (14)" : "?";
+}
+
 enum KClass { K_GEMM = 0, K_ATTN_PREFILL = 1, K_GEMV = 2, K_ATTN_DECODE = 3, K_LMHEAD = 4, K_MISC = 5, K_PERSIST = 6 };
 
 struct Seq {
@@ -259,6 +263,7 @@ struct ms_engine {
   bool qd(const QSlot* q, int M, int N, int K, int S, int epi) const {
     if (!qdgemm_mode || !q || !q->ready()) return false;
     const QMat& m = q->m;
+    if (m.type0 == MS_QT_Q8_0) return false;  // no packed Q8_0 skinny GEMM: the fp16 copies
     const bool q4 = m.type0 == MS_QT_Q4_K && (m.n < 2 || m.type1 == MS_QT_Q4_K) && (m.n < 3 || m.type2 == MS_QT_Q4_K);
     return (q4 || qdgemm_mode == 2) && qdgemm_supported(M, N, K, S, epi, m);
   }
@@ -692,6 +697,13 @@ struct ms_engine {
   // K-quant tensors loaded so far, (tensor, layer, ggml type) in load order: the manifest a
   // weight broadcast replays on the receiving ranks (ms_quant_manifest / ms_declare_weight_q)
   std::vector<std::array<int32_t, 3>> quant_manifest;
+  // an engine's quantised matrices are all Q8_0 or all K-quant (one decode arithmetic per engine)
+  void check_quant_family(int type) const {
+    for (const auto& q : quant_manifest)
+      REQUIRE((q[2] == MS_QT_Q8_0) == (type == MS_QT_Q8_0), MS_EINVAL,
+              std::string("ggml type ") + qtype_name(type) + " cannot join an engine that holds " + qtype_name(q[2]) +
+                  " tensors: an engine's quantised matrices are all Q8_0 (8) or all K-quant (Q4_K 12 / Q6_K 14)");
+  }
   void note_quant(int tensor, int layer, int type) {
     for (auto& q : quant_manifest)
       if (q[0] == tensor && q[1] == layer) { q[2] = type; return; }
@@ -1128,7 +1140,8 @@ static uint8_t* q_region(ms_engine& E, QSlot& s, int idx, int row0, int rows, in
 static void load_quant(ms_engine& E, int tensor, int layer, int type, const uint8_t* dblocks) {
   TensorDst t = tensor_dst(E, tensor, layer);
   REQUIRE(t.rows > 1, MS_EINVAL, "RMSNorm weights are not quantised");
-  REQUIRE(t.cols % 256 == 0, MS_EINVAL, "K-quant tensors need cols % 256 == 0");
+  REQUIRE(t.cols % 256 == 0, MS_EINVAL, "quantised tensors need cols % 256 == 0");
+  E.check_quant_family(type);
   // an untied embedding is only gathered: its fp16 copy is all decode needs
   uint8_t* q = t.qs ? q_region(E, *t.qs, t.qregion, t.qrow0, t.qrows, type, t.cols) : nullptr;
   launch_quant_rows(type, dblocks, t.rows, t.cols, t.dst, t.mul, t.add, q, t.qrow0, E.stream);
@@ -1148,7 +1161,7 @@ int ms_load_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t type, 
   return guarded(e, [&]() -> int {
     ms_engine& E = *e;
     REQUIRE(host != nullptr, MS_EINVAL, "null block buffer");
-    REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q6_K, MS_EINVAL, "ggml type must be Q4_K (12) or Q6_K (14)");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0 (8), Q4_K (12) or Q6_K (14)");
     HIP_OK(hipSetDevice(E.cfg.device));
     TensorDst t = tensor_dst(E, tensor, layer);
     const int64_t want = (int64_t)t.rows * (t.cols / 256) * qblock_bytes(type, false);
@@ -1175,10 +1188,11 @@ int ms_declare_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t typ
   e->drop_graphs();
   return guarded(e, [&]() -> int {
     ms_engine& E = *e;
-    REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q6_K, MS_EINVAL, "ggml type must be Q4_K (12) or Q6_K (14)");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0 (8), Q4_K (12) or Q6_K (14)");
     HIP_OK(hipSetDevice(E.cfg.device));
     TensorDst t = tensor_dst(E, tensor, layer);
-    REQUIRE(t.rows > 1 && t.cols % 256 == 0, MS_EINVAL, "not a K-quant matrix");
+    REQUIRE(t.rows > 1 && t.cols % 256 == 0, MS_EINVAL, "not a quantisable matrix");
+    E.check_quant_family(type);
     E.has_quant = true;
     if (t.qs) {  // the layout of a quantised load, without its bytes (a broadcast fills them)
       q_region(E, *t.qs, t.qregion, t.qrow0, t.qrows, type, t.cols);
@@ -1220,7 +1234,8 @@ static int q4_k_m_type(int tensor, int layer, int n_layers) {
   return MS_QT_Q4_K;
 }
 
-int ms_init_synthetic_q(ms_engine* e, uint64_t seed, float scale, float jitter) {
+// random blocks for every matrix: the Q4_K_M per-tensor mix (all_type 0) or one type throughout
+static int init_synthetic_quant(ms_engine* e, uint64_t seed, float scale, float jitter, int all_type) {
   if (!e) return MS_EINVAL;
   e->drop_graphs();
   return guarded(e, [&]() -> int {
@@ -1228,18 +1243,19 @@ int ms_init_synthetic_q(ms_engine* e, uint64_t seed, float scale, float jitter) 
     HIP_OK(hipSetDevice(E.cfg.device));
     hipStream_t s = E.stream;
     size_t maxb = 0;
+    const int braw = all_type ? qblock_bytes(all_type, false) : kQ6KBytes;  // the largest raw unit
     const int mats[] = {MS_T_WQ, MS_T_WK, MS_T_WV, MS_T_WO, MS_T_WGATE, MS_T_WUP, MS_T_WDOWN};
     for (int tsr : mats) {
       TensorDst t = tensor_dst(E, tsr, 0);
-      maxb = std::max(maxb, (size_t)t.rows * (t.cols / 256) * kQ6KBytes);
+      maxb = std::max(maxb, (size_t)t.rows * (t.cols / 256) * braw);
     }
-    maxb = std::max(maxb, (size_t)E.V * (E.H / 256) * kQ6KBytes);
+    maxb = std::max(maxb, (size_t)E.V * (E.H / 256) * braw);
     void* tmp = nullptr;
     HIP_OK(hipMalloc(&tmp, maxb));
     try {
       auto one = [&](int tsr, int l) {
         TensorDst t = tensor_dst(E, tsr, l);
-        const int ty = q4_k_m_type(tsr, l, E.L);
+        const int ty = all_type ? all_type : q4_k_m_type(tsr, l, E.L);
         launch_synth_qblocks(ty, (uint8_t*)tmp, (int64_t)t.rows * (t.cols / 256),
                              seed ^ ((uint64_t)tsr << 56) ^ ((uint64_t)l << 48), scale, s);
         load_quant(E, tsr, l, ty, (const uint8_t*)tmp);
@@ -1260,6 +1276,14 @@ int ms_init_synthetic_q(ms_engine* e, uint64_t seed, float scale, float jitter) 
     (void)hipFree(tmp);
     return MS_OK;
   });
+}
+
+int ms_init_synthetic_q(ms_engine* e, uint64_t seed, float scale, float jitter) {
+  return init_synthetic_quant(e, seed, scale, jitter, 0);
+}
+
+int ms_init_synthetic_q8_0(ms_engine* e, uint64_t seed, float scale, float jitter) {
+  return init_synthetic_quant(e, seed, scale, jitter, MS_QT_Q8_0);
 }
 
 int ms_init_synthetic(ms_engine* e, uint64_t seed, float std_, float jitter) {
@@ -2293,7 +2317,7 @@ int ms_op_residual_rmsnorm(float* x, const float* slabs, int32_t S, const void* 
 int ms_op_dequant(int32_t type, const void* blocks, int64_t n_blocks, float* out, void* stream) {
   return op_guard([&] {
     REQUIRE(blocks && out && n_blocks >= 1, MS_EINVAL, "bad dequant arguments");
-    REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q6_K, MS_EINVAL, "ggml type must be Q4_K or Q6_K");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K or Q6_K");
     launch_dequant_f32(type, (const uint8_t*)blocks, n_blocks, out, (hipStream_t)stream);
   });
 }
@@ -2302,7 +2326,7 @@ int ms_op_quant_rows(int32_t type, const void* blocks, int32_t rows, int32_t K, 
                      void* packed_out, void* stream) {
   return op_guard([&] {
     REQUIRE(blocks && f16_out && rows >= 1 && K >= 256 && K % 256 == 0, MS_EINVAL, "bad quant_rows arguments");
-    REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q6_K, MS_EINVAL, "ggml type must be Q4_K or Q6_K");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K or Q6_K");
     launch_quant_rows(type, (const uint8_t*)blocks, rows, K, (f16_t*)f16_out, 16, 0,
                       (uint8_t*)packed_out, 0, (hipStream_t)stream);
   });
@@ -2312,7 +2336,7 @@ int ms_op_qgemv(const void* X, int32_t type, const void* packed, void* out, int3
                 int32_t K, int32_t ldo, int32_t epi, void* stream) {
   return op_guard([&] {
     REQUIRE(X && packed && out && N >= 16, MS_EINVAL, "bad qgemv operands");
-    REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q6_K, MS_EINVAL, "ggml type must be Q4_K or Q6_K");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K or Q6_K");
     REQUIRE(((epi >= 0 && epi <= 3) || epi == MS_EPI_ARGMAX) && (epi != MS_EPI_SWIGLU || N % 32 == 0),
             MS_EINVAL, "bad epilogue");
     REQUIRE(qgemv_supported(M, N, K, epi, op_rs_tiles()), MS_EINVAL,
@@ -2332,7 +2356,7 @@ int ms_op_qgemv_split(const void* X, int32_t type, const void* packed, float* sl
                       int32_t N, int32_t K, int32_t S, void* stream) {
   return op_guard([&] {
     REQUIRE(X && packed && slabs && N >= 16 && S >= 1, MS_EINVAL, "bad qgemv_split operands");
-    REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q6_K, MS_EINVAL, "ggml type must be Q4_K or Q6_K");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K or Q6_K");
     REQUIRE(qgemv_split_supported(M, N, K, S, op_rs_tiles()), MS_EINVAL,
             "qgemv_split shape unsupported (M<=64, K%(256*S)==0, row-scale statistics within kRsStage and LDS)");
     QMat q{};
@@ -2350,6 +2374,8 @@ int ms_op_qdgemm(const void* X, int32_t type, const void* packed, void* out, int
                  int32_t S, int32_t ldo, int32_t epi, void* stream) {
   return op_guard([&] {
     REQUIRE(X && packed && out && N >= 64 && K >= 256 && S >= 1, MS_EINVAL, "bad qdgemm operands");
+    REQUIRE(type != MS_QT_Q8_0, MS_EINVAL,
+            "qdgemm has no Q8_0 form (Q8_0 engines run their fp16 copies in the large regime): Q4_K, Q6_K or F16");
     REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q6_K || type == 1, MS_EINVAL, "ggml type must be Q4_K, Q6_K or F16");
     REQUIRE(!g_op_rs.ssq || g_op_rs.tiles == 1, MS_EINVAL, "qdgemm row scale: one-tile statistics only");
     if (type == 1) {  // fp16 rows [N][K] through the same kernel

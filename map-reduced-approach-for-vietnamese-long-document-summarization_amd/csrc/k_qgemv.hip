@@ -29,6 +29,18 @@
 //     exact fp32 dequantised weights (no fp16 rounding of them, and no cancellation: a
 //     1024 + q bias form cost ~7e-6 relative against fp64);
 //   * Q6_K, dequantised in registers to the fp16 values of the fp16 copy.
+//
+// Q8_0 (ggml type 8, llama3.2:3b-instruct-q8_0) is the third weight form, counted in the same
+// 256-weight units: 8 consecutive ggml blocks {fp16 d; int8 qs[32]} = 272 raw bytes, y = d * q
+// (one fp32 multiply, exact: 11 x 8 significant bits).  Packed unit, 272 B, 16-B aligned:
+//   bytes 0..15                       the 8 fp16 scales d_0 .. d_7 in block order
+//   byte 16 + 64(s>>1) + 16g + 8(s&1) + i = q[32s + 8g + i]   (block s, lane group g, i < 8)
+// so load c of lane group g (16 B at 16 + 64c + 16g) holds its 8 weights of blocks 2c and
+// 2c + 1, and one wave load instruction reads 64 contiguous bytes of each row.  The GEMV runs one
+// MFMA per 32-weight block on q held as the exact fp16 integers -128 .. 127 (byte ^ 0x80 placed
+// under the exponent byte 0x64 is the fp16 1024 + (q + 128); one packed fp16 subtract of 1152
+// gives q, exact), A_b = sum_k x_k q_k, then acc = fma(d_b, A_b, acc) in fp32: the weights are
+// never rounded to fp16, out = sum_b d_b (sum_k x_k q_k).
 #include <algorithm>
 #include <cstdlib>
 
@@ -82,13 +94,22 @@ __device__ __forceinline__ float deq_q6k_one(const uint8_t* b, int t) {
   return __fmul_rn(__fmul_rn(d, (float)sc), (float)q);
 }
 
+// raw unit of 8 ggml Q8_0 blocks {fp16 d; int8 qs[32]}: weight t is element t & 31 of block t >> 5
+__device__ __forceinline__ float deq_q8_one(const uint8_t* b, int t) {
+  const uint8_t* blk = b + 34 * (t >> 5);
+  const float d = h2f_lo((uint32_t)blk[0] | ((uint32_t)blk[1] << 8));
+  return __fmul_rn(d, (float)(int)(int8_t)blk[2 + (t & 31)]);
+}
+
+__device__ __forceinline__ float deq_one(int type, const uint8_t* b, int t) {
+  return type == MS_QT_Q4_K ? deq_q4k_one(b, t) : type == MS_QT_Q8_0 ? deq_q8_one(b, t) : deq_q6k_one(b, t);
+}
+
 __global__ __launch_bounds__(256) void dequant_f32_kernel(int type, const uint8_t* __restrict__ blocks,
                                                           float* __restrict__ out) {
   const size_t sb = blockIdx.x;
   const int t = threadIdx.x;
-  const float y = (type == MS_QT_Q4_K) ? deq_q4k_one(blocks + sb * kQ4KBytes, t)
-                                       : deq_q6k_one(blocks + sb * kQ6KBytes, t);
-  out[sb * 256 + t] = y;
+  out[sb * 256 + t] = deq_one(type, blocks + sb * qblock_bytes(type, false), t);
 }
 
 void launch_dequant_f32(int type, const uint8_t* blocks, int64_t n_blocks, float* out, hipStream_t s) {
@@ -103,15 +124,21 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(int type, const uint8_t
                                                          uint8_t* __restrict__ dst_q, int q_row_base) {
   const int r = blockIdx.y, sb = blockIdx.x, t = threadIdx.x;
   const int nsb = K / 256;
-  const int braw = (type == MS_QT_Q4_K) ? kQ4KBytes : kQ6KBytes;
+  const int braw = qblock_bytes(type, false);
   const uint8_t* b = blocks + ((size_t)r * nsb + sb) * braw;
-  const float y = (type == MS_QT_Q4_K) ? deq_q4k_one(b, t) : deq_q6k_one(b, t);
+  const float y = deq_one(type, b, t);
   const size_t drow = map_row(r, map_mul, map_add);
   dst_f16[drow * K + (size_t)sb * 256 + t] = f2h(y);
   if (dst_q) {
-    const int bp = (type == MS_QT_Q4_K) ? kQ4KBytes : kQ6KPacked;
+    const int bp = qblock_bytes(type, true);
     uint8_t* q = dst_q + ((drow - q_row_base) * nsb + sb) * bp;
-    if (type == MS_QT_Q4_K) {
+    if (type == MS_QT_Q8_0) {
+      // the 8 scales, then quant byte 16 + 64(s >> 1) + 16g + 8(s & 1) + i = q[32s + 8g + i]: lane
+      // group g's weights of blocks 2c, 2c + 1 in one 16-B load at 16 + 64c + 16g (file header)
+      if (t < 16) q[t] = b[34 * (t >> 1) + (t & 1)];
+      const int s_ = t >> 5, g = (t >> 3) & 3, i = t & 7;
+      q[16 + 64 * (s_ >> 1) + 16 * g + 8 * (s_ & 1) + i] = b[34 * s_ + 2 + (t & 31)];
+    } else if (type == MS_QT_Q4_K) {
       // header as is; quant byte 16 + 64(s >> 2) + 16g + 4(s & 3) + i = q[k] | q[k + 4] << 4,
       // k = 32s + 8g + i: lane group g's sub-blocks 0-3 at 16 + 16g, 4-7 at 80 + 16g, so one wave
       // load instruction reads 64 contiguous bytes of each row
@@ -160,7 +187,7 @@ __device__ __forceinline__ uint64_t smix(uint64_t z) {
 
 __global__ void synth_qblocks_kernel(int type, uint8_t* __restrict__ blocks, int64_t n_blocks,
                                      uint64_t seed_h, float scale) {
-  const int braw = (type == MS_QT_Q4_K) ? kQ4KBytes : kQ6KBytes;
+  const int braw = qblock_bytes(type, false);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_blocks;
        i += (int64_t)gridDim.x * blockDim.x) {
     uint8_t* b = blocks + i * braw;
@@ -175,6 +202,15 @@ __global__ void synth_qblocks_kernel(int type, uint8_t* __restrict__ blocks, int
       const _Float16 dm = (_Float16)((float)d * 7.5f);
       const uint16_t db = __builtin_bit_cast(uint16_t, d), dmb = __builtin_bit_cast(uint16_t, dm);
       b[0] = db & 0xFF; b[1] = db >> 8; b[2] = dmb & 0xFF; b[3] = dmb >> 8;
+    } else if (type == MS_QT_Q8_0) {
+      // uniform int8 quants have std 73.9; the 8 blocks' scales spread over [0.5, 1.5) scale / 74
+      // (std of the weights 1.04 scale), positive normal fp16 for any scale >= 5e-3
+      uint64_t hs = smix(h ^ 0x51ull);
+      for (int k = 0; k < 8; ++k) {
+        const float uk = 0.5f + (float)((hs >> (8 * k)) & 0xFF) * (1.0f / 256.0f);
+        const uint16_t db = __builtin_bit_cast(uint16_t, (_Float16)(uk * scale / 74.f));
+        b[34 * k] = db & 0xFF; b[34 * k + 1] = db >> 8;
+      }
     } else {
       for (int k = 0; k < 16; ++k) b[192 + k] = (uint8_t)((int)(b[192 + k] & 0x7F) - 64);
       const _Float16 d = (_Float16)(u * scale / 680.f);
@@ -191,16 +227,67 @@ void launch_synth_qblocks(int type, uint8_t* blocks, int64_t n_blocks, uint64_t 
 }
 
 // ---------------------------------------------------------------- dequant-fused GEMV
+// one packed Q8_0 unit of this lane's row: the 8 scales and lane group g's four 16-B quant pieces
+struct Q8Regs {
+  uint4 sc, q[4];
+};
+// tile: the block-uniform address of the tile's first row (a scalar base for the loads); row, sb:
+// this lane's row in the tile and unit in the row (a 32-bit lane offset)
+__device__ __forceinline__ void q8_fetch(Q8Regs& r, const uint8_t* tile, int row_bytes, int row, int sb, int g) {
+  const uint32_t o = (uint32_t)(row * row_bytes + sb * kQ8Bytes);
+  const uint8_t* qp = tile + (o + 16u + 16u * (uint32_t)g);  // one 32-bit lane offset per address
+  r.sc = ldw16(tile + o);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) r.q[c] = ldw16(qp + 64 * c);
+}
+// the same in two halves (the grid-stride loop's prefetch): the scales and blocks 0-3, blocks 4-7.
+// Here the tile is a 32-bit byte offset from the matrix base (the launcher checks the matrix is
+// < 4 GiB): scalar base + 32-bit lane offsets, where 64-bit lane addresses carried across the
+// loop (4 VGPRs) spilled
+template <int HALF>
+__device__ __forceinline__ void q8_fetch_half(Q8Regs& r, const uint8_t* base, uint32_t tile, int row_bytes, int row, int sb,
+                                              int g) {
+  const uint32_t o = tile + (uint32_t)(row * row_bytes + sb * kQ8Bytes);
+  const uint8_t* qp = base + (o + 16u + 16u * (uint32_t)g);
+  if constexpr (HALF == 0) r.sc = ldw16(base + o);
+#pragma unroll
+  for (int c = 2 * HALF; c < 2 * HALF + 2; ++c) r.q[c] = ldw16(qp + 64 * c);
+}
+__device__ __forceinline__ float q8_scale(const Q8Regs& r, int s) {  // s compile-time
+  const uint32_t w = (s >> 1) == 0 ? r.sc.x : (s >> 1) == 1 ? r.sc.y : (s >> 1) == 2 ? r.sc.z : r.sc.w;
+  return h2f_lo(w >> (16 * (s & 1)));
+}
+// block s's 8 int8 weights of this lane group as the exact fp16 integers: byte ^ 0x80 under the
+// exponent byte 0x64 is the fp16 1024 + (q + 128) (perm selector 4 = byte 0 of the constant),
+// and 1024 + (q + 128) - 1152 = q with no rounding (q = -128: 1024 - 1152)
+__device__ __forceinline__ f16x8 q8_frag(const Q8Regs& r, int s) {  // s compile-time
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+  const uint4 v = r.q[s >> 1];
+  const uint32_t w0 = ((s & 1) ? v.z : v.x) ^ 0x80808080u, w1 = ((s & 1) ? v.w : v.y) ^ 0x80808080u;
+  const h2 bias = {(_Float16)1152.0f, (_Float16)1152.0f};
+  auto cv = [&](uint32_t w, uint32_t sel) {
+    const h2 u = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, w, sel));
+    return __builtin_bit_cast(uint32_t, u - bias);
+  };
+  const u4v pk = {cv(w0, 0x04010400u), cv(w0, 0x04030402u), cv(w1, 0x04010400u), cv(w1, 0x04030402u)};
+  return __builtin_bit_cast(f16x8, pk);
+}
+
 // One block per 16*NT rows, waves split the K/256 super-blocks (SBW per wave).  Lane
 // group g = lane>>4 owns 64 weights of each super-block:
 //   Q4_K: chunk g (qs bytes 32g..32g+31): low nibbles = weights 64g..64g+31 (sub-block
 //         2g), high nibbles = 64g+32.. (sub-block 2g+1);
 //   Q6_K: half h = g>>1, positions l in [16p, 16p+16), p = g&1, each giving the four
 //         weights h*128 + {0,32,64,96} + l.
+//   Q8_0: weights 32s + 8g .. +7 of each of the unit's 8 blocks s (Q4_K's order).
 // MFMA t of a super-block takes 8 of those weights per lane and the X elements of the
 // same k -- a k permutation applied to both operands, so every dot product is unchanged.
 // XM: the X source (gemv_common.h kXGlobal / kXLds / kXRegs, as in k_gemv.hip)
-template <int MT, int NT, int EPI, int SBW, int XM, bool RS>
+// QF: 0 = K-quant regions (Q4_K / Q6_K chosen per region at run time), MS_QT_Q8_0 = a Q8_0 matrix
+// (its own instantiations: as a third run-time branch it raised the registers and the scratch of
+// every K-quant instantiation, the kernel's allocation being the largest branch's)
+template <int QF, int MT, int NT, int EPI, int SBW, int XM, bool RS>
 __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X, QMat qm,
                                                      void* __restrict__ out, int M, int N, int K,
                                                      int ldo, int rinv_off, GemvArgs ga) {
@@ -243,7 +330,7 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
   // Q6_K MFMA t: k = j*256 + hh*128 + (t>>1)*32 + 16p + 8(t&1)
   f16x8 xr[XR ? SBW : 1][XR ? 8 : 1][XR ? MT : 1];
   if constexpr (XR) {
-    const bool q6 = type != MS_QT_Q4_K;
+    const bool q6 = QF != MS_QT_Q8_0 && type != MS_QT_Q4_K;  // Q8_0 blocks take Q4_K's k order
 #pragma unroll
     for (int j = 0; j < SBW; ++j)
 #pragma unroll
@@ -256,7 +343,42 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
         }
   }
   __builtin_amdgcn_sched_barrier(0);
-  if (type == MS_QT_Q4_K) {
+  if constexpr (QF == MS_QT_Q8_0) {  // packed 272-B units: 8 scales, 4 x 64 B of regrouped quants
+    Q8Regs w[SBW][NT];
+#pragma unroll
+    for (int j = 0; j < SBW; ++j)
+#pragma unroll
+      for (int n = 0; n < NT; ++n)
+        q8_fetch(w[j][n], base + (size_t)(rbase + n * 16) * row_bytes + (size_t)sbk * kQ8Bytes, row_bytes, frw,
+                 sb0 + j, g);
+    if constexpr (XL) {  // the X image has landed once at most the weight loads are pending
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_waitcnt(vmcnt_imm(5 * SBW * NT));
+      __builtin_amdgcn_s_barrier();  // no fence: a fence would wait for the weight loads too
+    }
+#pragma unroll
+    for (int j = 0; j < SBW; ++j)
+#pragma unroll
+      for (int s_ = 0; s_ < 8; ++s_) {
+        const int k = ((sb0 + j) * 8 + s_) * 32 + 8 * g;  // as Q4_K: block s_, this lane group's 8 weights
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          const float d = q8_scale(w[j][n], s_);
+          const f16x8 wf = q8_frag(w[j][n], s_);
+#pragma unroll
+          for (int m = 0; m < MT; ++m) {
+            const int xrow = min(m * 16 + fr, M - 1);
+            const f16x8 xf = XR ? xr[XR ? j : 0][XR ? s_ : 0][XR ? m : 0]
+                            : XL ? *(const f16x8*)(smem + x_lds(xrow, k, K))
+                                 : *(const f16x8*)(X + (size_t)xrow * ldx + k);
+            // A_b = sum_k x_k q_k on the exact integers, then one fp32 FMA per output element
+            const f32x4 A = mfma16(xf, wf, f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[m][n][i] = __fmaf_rn(d, A[i], acc[m][n][i]);
+          }
+        }
+      }
+  } else if (type == MS_QT_Q4_K) {
     uint4 hq[SBW][NT], q0[SBW][NT], q1[SBW][NT];
 #pragma unroll
     for (int j = 0; j < SBW; ++j)
@@ -483,6 +605,90 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   }
 }
 
+// ---- the Q8_0 lm_head (418 MB, the largest stream of a Q8_0 step) in the same form: resident
+// blocks stage X and the norm factors once and walk tiles b, b + G, ... with the next tile's 5
+// loads in flight under the current tile's 8 MFMAs -- issued in two halves, the second once
+// blocks 0-3 are multiplied and their 8 VGPRs free (both tiles whole, 40 VGPRs, spilled under
+// the 80-VGPR cap of two resident 12-wave blocks per CU).  Per tile the arithmetic is
+// qgemv_kernel<Q8_0, 1, 1, ARGMAX, 1, LDS, false>'s exactly: bit-identical partials.
+__global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(6, 8))) void qgemv_q8_argmax_gs_kernel(const f16_t* __restrict__ X, QMat qm,
+                                                                float2* __restrict__ out, int M, int N, int K,
+                                                                int ldo, int red_off, int rinv_off, GemvArgs ga) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int ELEMS = 256;  // MT = NT = 1
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int fr = lane & 15, g = lane >> 4;
+  const int tiles = N / 16, G = gridDim.x;
+  const uint8_t* base = qm.base0;
+  const int row_bytes = qm.row_bytes0;
+  // 0. row statistics and X once per block, then the first tile's weights
+  const bool rs_on = ga.rs.ssq != nullptr;
+  if (rs_on) rs_begin<false>(smem, rinv_off, ga.rs, M);
+  gemv_dma_x(smem, X, M, K, K);
+  __builtin_amdgcn_sched_barrier(0);
+  Q8Regs cur, nxt;
+  int t = blockIdx.x;
+  q8_fetch(cur, base + (size_t)t * 16 * row_bytes, row_bytes, fr, wave, g);
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(vmcnt_imm(5));  // X and the statistics landed (issued first)
+  __builtin_amdgcn_s_barrier();
+  float* rinv = (float*)(smem + rinv_off);
+  if (rs_on) rs_finish<false>(smem, rinv_off, ga.rs, M, 0.f);
+  lds_sync();
+  float* red = (float*)(smem + red_off);
+  // this lane's X fragment of block s_: chunk (wave * 32 + 4 s_ + g) ^ (row & 7) of its row; the
+  // swizzle touches chunk bits 0-2 only, so block s_ sits 128 (s_ >> 1) bytes behind block s_ & 1
+  // (two addresses live across the tile loop instead of eight)
+  const int xrow = min(fr, M - 1);
+  const char* xs0 = smem + x_lds(xrow, wave * 256 + 8 * g, K);
+  const char* xs1 = smem + x_lds(xrow, wave * 256 + 32 + 8 * g, K);
+  for (; t < tiles; t += G) {
+    const bool more = t + G < tiles;
+    const uint32_t ntile = (uint32_t)(t + G) * 16u * (uint32_t)row_bytes;
+    if (more) q8_fetch_half<0>(nxt, base, ntile, row_bytes, fr, wave, g);
+    __builtin_amdgcn_sched_barrier(0);
+    // qgemv_kernel's Q8_0 body, SBW = 1 (this wave's unit = its index), MT = NT = 1; the waits
+    // for `cur` are the compiler's own (register dependencies: no DMA is in flight here)
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s_ = 0; s_ < 8; ++s_) {
+      if (s_ == 4) {
+        if (more) q8_fetch_half<1>(nxt, base, ntile, row_bytes, fr, wave, g);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const float d = q8_scale(cur, s_);
+      const f16x8 xf = *(const f16x8*)(((s_ & 1) ? xs1 : xs0) + 128 * (s_ >> 1));
+      const f32x4 A = mfma16(xf, q8_frag(cur, s_), f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[i] = __fmaf_rn(d, A[i], acc[i]);
+      // two blocks' products in flight at most: all eight cost 32 VGPRs and spilled the prefetch
+      if (s_ & 1) __builtin_amdgcn_sched_barrier(0);
+    }
+    // cross-wave reduction (LDS-only barriers: the next tile's loads stay in flight)
+    *(f32x4*)&red[wave * ELEMS + lane * 4] = acc;
+    lds_sync();
+    if ((int)threadIdx.x < ELEMS) {
+      const int e = threadIdx.x, l = (e >> 2) & 63, j = e & 3;
+      const int row = 4 * (l >> 4) + j, col = t * 16 + (l & 15);
+      float v = -INFINITY;
+      if (row < M && col < N) {
+        float sum = 0.f;
+        for (int q = 0; q < nw; ++q) sum += red[q * ELEMS + e];
+        v = sum * (rs_on ? rinv[row] : 1.0f);
+      }
+      if (!(v == v)) v = -INFINITY;
+      int idx = col;
+#pragma unroll
+      for (int o = 4; o < 64; o <<= 1) amax_merge_dev(v, idx, __shfl_xor(v, o, 64), __shfl_xor(idx, o, 64));
+      // (a 32-bit offset from the scalar base: a 64-bit lane address held across the loop spilled)
+      if ((l & 15) == 0 && row < M)
+        *(float2*)((char*)out + (uint32_t)(row * ldo + t) * 8u) = make_float2(v, __int_as_float(idx));
+    }
+    lds_sync();  // red is rewritten by the next tile
+    cur = nxt;
+  }
+}
+
 // ---- the Q4_K gate/up projection (SwiGLU epilogue) in the same grid-stride form: 256 blocks
 // of 12 waves (wave w = super-block w of the 3072-long rows) take X into registers ONCE (the
 // one-tile kernel's 512 blocks each re-read the 8 x 3072 X -- 49 MB of L2 traffic against
@@ -587,14 +793,18 @@ __global__ __launch_bounds__(768) void qgemv_q4_swiglu_gs_kernel(const f16_t* __
   }
 }
 
-// which K-quant GEMVs take the grid-stride form: MS_QGEMV_GS bit 0 the Q6_K lm_head argmax,
-// bit 1 the Q4_K gate/up (default: both; ms_set_qgemv_gs(0): one-tile blocks everywhere).  The
+// which quantised GEMVs take the grid-stride form: MS_QGEMV_GS bit 0 the Q6_K lm_head argmax,
+// bit 1 the Q4_K gate/up, bit 2 the Q8_0 lm_head argmax (default 3: the two K-quant forms;
+// ms_set_qgemv_gs(1): all three, (0): one-tile blocks everywhere).  The Q8_0 form is off by
+// default: it measured slower than the one-tile blocks, 99.4 vs 86.3 us per lm_head launch at 8
+// slots (profiles/q8_0/) -- a tile is 8 MFMAs per wave, too little work to cover the two block
+// barriers and the prefetch wait each tile costs, where Q6_K's dequantisation covers them.  The
 // same form for the single-type split-K slab projections (O, down: X slice staged once per
 // block) measured slower -- O 5.10 -> 6.04 us, down 8.89 -> 9.4-10.7 us, decode 1.806 -> 1.871
 // ms per Q4_K_M step (profiles/r04/v25_*): those launches are one latency each, and fewer
 // blocks leave fewer weight bytes in flight.
 static int g_q_gs = -1;
-void set_qgemv_gs(bool on) { g_q_gs = on ? 3 : 0; }
+void set_qgemv_gs(bool on) { g_q_gs = on ? 7 : 0; }
 static int q_gs_mask() {
   if (g_q_gs < 0) {
     const char* e = getenv("MS_QGEMV_GS");
@@ -604,6 +814,7 @@ static int q_gs_mask() {
 }
 static bool q6_gs_on() { return (q_gs_mask() & 1) != 0; }
 static bool q4_gs_on() { return (q_gs_mask() & 2) != 0; }
+static bool q8_gs_on() { return (q_gs_mask() & 4) != 0; }
 
 
 struct QPlan {
@@ -679,16 +890,25 @@ static void qgemv_go(const f16_t* X, const QMat& q, void* out, int M, int N, int
     const bool xl = qx_in_lds(M, K, ga.rs);
     constexpr bool kRsEpi = gemv_rs_epi<EPI>();
     const bool rs = kRsEpi && ga.rs.ssq != nullptr;
+    const bool q8 = q.type0 == MS_QT_Q8_0;  // an engine's matrices are all Q8_0 or all K-quant
+#define QLF(SBW_, XM_, RS_)                                                                                   \
+    do {                                                                                                      \
+      if (q8)                                                                                                 \
+        MS_LAUNCH((qgemv_kernel<MS_QT_Q8_0, MT, NT, EPI, SBW_, XM_, RS_>), grid, blk, lds, s, X, q, out, M, N, K, \
+                  ldo, ro, ga);                                                                               \
+      else                                                                                                    \
+        MS_LAUNCH((qgemv_kernel<0, MT, NT, EPI, SBW_, XM_, RS_>), grid, blk, lds, s, X, q, out, M, N, K, ldo, ro, \
+                  ga);                                                                                        \
+    } while (0)
 #define QL(SBW_, XM_)                                                                                         \
     do {                                                                                                      \
       if constexpr (kRsEpi) {                                                                                 \
         if (rs) {                                                                                             \
-          MS_LAUNCH((qgemv_kernel<MT, NT, EPI, SBW_, XM_, true>), grid, blk, lds, s, X, q, out, M, N, K, ldo, ro, \
-                    ga);                                                                                      \
+          QLF(SBW_, XM_, true);                                                                               \
           break;                                                                                              \
         }                                                                                                     \
       }                                                                                                       \
-      MS_LAUNCH((qgemv_kernel<MT, NT, EPI, SBW_, XM_, false>), grid, blk, lds, s, X, q, out, M, N, K, ldo, ro, ga); \
+      QLF(SBW_, XM_, false);                                                                                  \
     } while (0)
     if (p.SBW == 2 && xl) QL(2, kXLds);
     else if (p.SBW == 2) QL(2, kXGlobal);
@@ -696,6 +916,7 @@ static void qgemv_go(const f16_t* X, const QMat& q, void* out, int M, int N, int
     else if (!qx_in_regs(p)) QL(1, kXGlobal);
     else if constexpr (MT == 1) QL(1, kXRegs);
 #undef QL
+#undef QLF
   }
 }
 
@@ -721,8 +942,10 @@ void launch_qgemv(const f16_t* X, const QMat& q, void* out, int M, int N, int K,
   GemvArgs ga{};
   if (ga_in) ga = *ga_in;
   // (both grid-stride kernels finish a tile with one thread per element: >= 4 waves)
-  if (epi == MS_GEMV_EPI_ARGMAX && q6_gs_on() && q.n == 1 && q.type0 == MS_QT_Q6_K && p.MT == 1 && p.SBW == 1 &&
-      p.waves >= 4 && N % 16 == 0) {
+  const bool lm_q6 = q6_gs_on() && q.type0 == MS_QT_Q6_K, lm_q8 = q8_gs_on() && q.type0 == MS_QT_Q8_0;
+  if (epi == MS_GEMV_EPI_ARGMAX && (lm_q6 || lm_q8) && q.n == 1 && p.MT == 1 && p.SBW == 1 &&
+      p.waves >= 4 && p.waves <= 12 && N % 16 == 0 &&  // (the kernels' launch bounds: 12 waves)
+      (!lm_q8 || (uint64_t)N * (uint64_t)q.row_bytes0 < (1ull << 32))) {  // (its 32-bit tile offsets)
     ga.rs = RowScale{};  // as qgemv_go: a row's positive scale never moves its argmax
     // LDS: [X image][per-wave partials][rinv][staged statistics]
     const int red_off = (int)((gemv_x_lds_bytes(M, K) + 15) / 16 * 16);
@@ -731,8 +954,12 @@ void launch_qgemv(const f16_t* X, const QMat& q, void* out, int M, int N, int K,
     const size_t lds = gemv_lds_total(main_bytes, ga.rs, M);
     if (lds <= kLdsCap) {
       const int grid = std::min(N / 16, 512);  // two resident blocks per CU
-      MS_LAUNCH(qgemv_q6_argmax_gs_kernel, dim3(grid), dim3(64 * p.waves), lds, s, X, q, (float2*)out, M, N, K, ldo,
-                red_off, ro, ga);
+      if (lm_q8)
+        MS_LAUNCH(qgemv_q8_argmax_gs_kernel, dim3(grid), dim3(64 * p.waves), lds, s, X, q, (float2*)out, M, N, K,
+                  ldo, red_off, ro, ga);
+      else
+        MS_LAUNCH(qgemv_q6_argmax_gs_kernel, dim3(grid), dim3(64 * p.waves), lds, s, X, q, (float2*)out, M, N, K,
+                  ldo, red_off, ro, ga);
       return;
     }
   }

@@ -166,7 +166,8 @@ void launch_gemm(const f16_t* A, const f16_t* W, void* out, int M, int N, int K,
 // tile choice: 0 = heuristic (256x256 8-phase for M, N >= 1024), 1 = 128x128, 2 = 256x256,
 // 3 = 256x256 on 4 waves, 4 (default) = the heuristic with 3 for the stored epilogues
 void set_gemm_variant(int v);
-// the Q6_K lm_head argmax GEMV: grid-stride two-stage loop (default) or one-tile blocks
+// the grid-stride two-stage quantised GEMVs (Q6_K / Q8_0 lm_head argmax, Q4_K gate/up): all on
+// or one-tile blocks everywhere (the library starts with the K-quant forms on, Q8_0's off)
 void set_qgemv_gs(bool on);
 // decode attention: the combine's XCD-matched grid (1, default) or the (B, Hq) grid (0) --
 // placement only, the same bits (order: 0; the prologue-wave form was removed in round 6)
@@ -259,10 +260,13 @@ void launch_dgemm(const f16_t* X, const f16_t* W, void* out, int M, int N, int K
                   hipStream_t s, const RowScale* rs = nullptr, int kh = 0, int wn = 0);
 int dgemm_kh_setting();
 
-// ---- ggml K-quant weights (k_qgemv.hip)
-enum { MS_QT_Q4_K = 12, MS_QT_Q6_K = 14 };  // ggml_type ids
+// ---- ggml quantised weights (k_qgemv.hip): the K-quants and Q8_0
+enum { MS_QT_Q8_0 = 8, MS_QT_Q4_K = 12, MS_QT_Q6_K = 14 };  // ggml_type ids
 constexpr int kQ4KBytes = 144, kQ6KBytes = 210, kQ6KPacked = 224;
-// up to 3 row regions of one fused matrix, each of a single K-quant type (flat fields:
+// Q8_0 counted in the K-quants' 256-weight units: 8 ggml blocks {fp16 d; int8 qs[32]} = 272 B raw,
+// and 272 B packed (the 8 scales, then the 256 quants regrouped: quant_rows_kernel)
+constexpr int kQ8Bytes = 272;
+// up to 3 row regions of one fused matrix, each of a single quant type (flat fields:
 // no runtime-indexed kernel-argument arrays)
 struct QMat {
   int n;
@@ -287,9 +291,10 @@ inline uint64_t smix_host(uint64_t z) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-inline int qblock_bytes(int type, bool packed) {
-  return type == MS_QT_Q4_K ? kQ4KBytes : (packed ? kQ6KPacked : kQ6KBytes);
+__host__ __device__ inline int qblock_bytes(int type, bool packed) {
+  return type == MS_QT_Q4_K ? kQ4KBytes : type == MS_QT_Q8_0 ? kQ8Bytes : (packed ? kQ6KPacked : kQ6KBytes);
 }
+inline bool qtype_known(int type) { return type == MS_QT_Q4_K || type == MS_QT_Q6_K || type == MS_QT_Q8_0; }
 void launch_dequant_f32(int type, const uint8_t* blocks, int64_t n_blocks, float* out, hipStream_t s);
 // raw ggml rows [rows][K/256 blocks] -> fp16 rows of a fused matrix (map_row) and, if dst_q,
 // packed quantised rows at (map_row(r) - q_row_base)

@@ -259,6 +259,10 @@ class Engine(RequestQueue):
         """Random Q4_K/Q6_K blocks in the Q4_K_M per-tensor mix (BASELINE config 5)."""
         self._chk(self.lib.ms_init_synthetic_q(self.h, seed, scale, norm_jitter), "ms_init_synthetic_q")
 
+    def init_synthetic_q8_0(self, seed: int = 2, scale: float = 0.02, norm_jitter: float = 0.0):
+        """Random Q8_0 blocks for every matrix, dequantised weights of std ~ scale (bench)."""
+        self._chk(self.lib.ms_init_synthetic_q8_0(self.h, seed, scale, norm_jitter), "ms_init_synthetic_q8_0")
+
     def load_tensor_q(self, tensor: int, layer: int, ggml_type: int, blocks: np.ndarray):
         b = np.ascontiguousarray(blocks, dtype=np.uint8)
         self._chk(self.lib.ms_load_weight_q(self.h, tensor, layer, ggml_type, b.ctypes.data, b.size),
