@@ -92,7 +92,9 @@ typedef struct ms_config {
                                    >= 192 + the fp16-rows K-quant GEMM form;
                                    K-quant: 1-16 residual-fused Q-GEMV, 17-64
                                    split Q-GEMV + residual_rmsnorm, >= 65 the
-                                   K-quant skinny GEMM, lm_head tile from 96;
+                                   K-quant skinny GEMM (all-Q4_K and all-Q5_K
+                                   matrices; the others their fp16 copies),
+                                   lm_head tile from 96;
                                    Q8_0: 1-16 residual-fused Q-GEMV, 17-64 split
                                    Q-GEMV + residual_rmsnorm in row groups of
                                    <= 64 (the exact d*q weights), >= 65 the fp16
@@ -151,14 +153,15 @@ int ms_load_weight(ms_engine* e, int32_t tensor, int32_t layer, const uint16_t* 
 /* device-side counter-based N(0,std)-like init; restated in oracle/synth.py */
 int ms_init_synthetic(ms_engine* e, uint64_t seed, float std, float norm_jitter);
 
-/* ggml quantised weights: the K-quants (Q4_K_M files: BASELINE.json config 5) and Q8_0
- * (llama3.2:3b-instruct-q8_0).  `blocks` are the tensor's rows as raw ggml blocks (Q4_K =
- * 144 B, Q6_K = 210 B per 256 weights; Q8_0 = 34 B per 32 weights, so rows * (cols / 32) * 34
- * bytes).  The engine keeps f16(dequant) for prefill and the blocks for the dequant-fused
+/* ggml quantised weights: the K-quants Q4_K / Q5_K / Q6_K (Q4_K_M files: BASELINE.json config 5;
+ * the q5_K_M, q5_K_S and q4_K_S mixes) and Q8_0 (llama3.2:3b-instruct-q8_0).  `blocks` are the
+ * tensor's rows as raw ggml blocks (Q4_K = 144 B, Q5_K = 176 B, Q6_K = 210 B per 256 weights;
+ * Q8_0 = 34 B per 32 weights, so rows * (cols / 32) * 34 bytes).  The engine keeps f16(dequant) for prefill and the blocks for the dequant-fused
  * decode GEMV.  RMSNorm weights stay fp16 (ms_load_weight).  An engine's quantised matrices
  * are all Q8_0 or all K-quant: the other family is refused with MS_EINVAL. */
 #define MS_GGML_Q8_0 8
 #define MS_GGML_Q4_K 12
+#define MS_GGML_Q5_K 13
 #define MS_GGML_Q6_K 14
 int ms_load_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t ggml_type,
                      const void* host_blocks, int64_t n_bytes);
@@ -166,6 +169,8 @@ int ms_load_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t ggml_t
 int ms_init_synthetic_q(ms_engine* e, uint64_t seed, float scale, float norm_jitter);
 /* random Q8_0 blocks for every matrix, dequantised weights of std ~ scale (bench) */
 int ms_init_synthetic_q8_0(ms_engine* e, uint64_t seed, float scale, float norm_jitter);
+/* random Q5_K/Q6_K blocks in the Q5_K_M mix: Q4_K_M's per-tensor types with Q5_K for Q4_K (bench) */
+int ms_init_synthetic_q5_k_m(ms_engine* e, uint64_t seed, float scale, float norm_jitter);
 
 /* ---- weight broadcast (one process per GPU: rank 0 loads, the others receive over RCCL) -- */
 /* every device weight buffer in a fixed order (fp16 matrices and norms, then K-quant
@@ -349,11 +354,11 @@ int ms_op_gemv_split(const void* X, const void* W, float* slabs, int32_t M, int3
    normalised projection that follows: y fp16 = f16(x * w * 2^-4), ssq[r] = sum of x[r]^2 (one tile) */
 int ms_op_residual_rmsnorm(float* x, const float* slabs, int32_t S, const void* w, void* y, float* ssq,
                            int32_t rows, int32_t hidden, void* stream);
-/* quantised-weight ops (Q4_K, Q6_K, Q8_0): raw ggml blocks -> fp32 (bit-exact restatement of
-   llama.cpp's dequantize_row_q4_K/q6_K/q8_0; n_blocks counts 256-weight units, for Q8_0 8 ggml
+/* quantised-weight ops (Q4_K, Q5_K, Q6_K, Q8_0): raw ggml blocks -> fp32 (bit-exact restatement of
+   llama.cpp's dequantize_row_q4_K/q5_K/q6_K/q8_0; n_blocks counts 256-weight units, for Q8_0 8 ggml
    blocks = 272 B each); raw rows -> fp16 rows + packed rows (Q6_K repacked to 224 B, Q8_0 to
-   272 B units: 8 scales, then the regrouped quants); dequant-fused GEMV over packed rows (same
-   epilogues as ms_op_gemv) */
+   272 B units: 8 scales, then the regrouped quants, Q5_K to header | Q4_K-order nibbles | qh);
+   dequant-fused GEMV over packed rows (same epilogues as ms_op_gemv) */
 int ms_op_dequant(int32_t ggml_type, const void* blocks, int64_t n_blocks, float* out, void* stream);
 int ms_op_quant_rows(int32_t ggml_type, const void* blocks, int32_t rows, int32_t K, void* f16_out,
                      void* packed_out, void* stream);
@@ -363,11 +368,16 @@ int ms_op_qgemv(const void* X, int32_t ggml_type, const void* packed_rows, void*
    (the quantised counterpart of ms_op_gemv_split; K % (256*S) == 0) */
 int ms_op_qgemv_split(const void* X, int32_t ggml_type, const void* packed_rows, float* slabs,
                       int32_t M, int32_t N, int32_t K, int32_t S, void* stream);
+/* ms_op_gemv_resid over packed quantised rows (the residual-fused O / down of quantised engines of
+   <= 16 slots): same outputs, M <= 16 */
+int ms_op_qgemv_resid(const void* X, int32_t ggml_type, const void* packed_rows, float* x, void* xg_out,
+                      const void* gamma, float* ssq_out, int32_t M, int32_t N, int32_t K, int32_t rt,
+                      void* stream);
 /* large-batch K-quant decode GEMM (M <= 256 rows): ms_op_dgemm over the packed rows, each weight
    dequantised in registers to its fp16-copy value f16(ggml dequant); epilogues MS_EPI_STORE_F32
    (S > 1: split-K slabs [S][M][N]), MS_EPI_SWIGLU, MS_EPI_ARGMAX; N % 64 == 0, K % (256 S) == 0
    with K / (256 S) even or a multiple of 3 (the engine's K-quant decode projections in engines
-   of >= 65 slots).  Q4_K, Q6_K or F16 (1) rows: Q8_0 has no form here (MS_EINVAL) */
+   of >= 65 slots).  Q4_K, Q5_K, Q6_K or F16 (1) rows: Q8_0 has no form here (MS_EINVAL) */
 int ms_op_qdgemm(const void* X, int32_t ggml_type, const void* packed_rows, void* out, int32_t M,
                  int32_t N, int32_t K, int32_t S, int32_t ldo, int32_t epilogue, void* stream);
 /* the input of a normalised projection: y fp16 [rows][hidden] = f16(x * w * 2^-4) and ssq[r] = sum

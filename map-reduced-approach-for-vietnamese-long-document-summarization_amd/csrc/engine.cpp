@@ -75,7 +75,11 @@ struct MsError : std::runtime_error {
   } while (0)
 
 const char* qtype_name(int type) {
-  return type == MS_QT_Q8_0 ? "Q8_0 (8)" : type == MS_QT_Q4_K ? "Q4_K (12)" : type == MS_QT_Q6_K ? "Q6_K (14)" : "?";
+  return type == MS_QT_Q8_0   ? "Q8_0 (8)"
+         : type == MS_QT_Q4_K ? "Q4_K (12)"
+         : type == MS_QT_Q5_K ? "Q5_K (13)"
+         : type == MS_QT_Q6_K ? "Q6_K (14)"
+                              : "?";
 }
 
 enum KClass { K_GEMM = 0, K_ATTN_PREFILL = 1, K_GEMV = 2, K_ATTN_DECODE = 3, K_LMHEAD = 4, K_MISC = 5, K_PERSIST = 6 };
@@ -238,9 +242,12 @@ struct ms_engine {
   // step at 128 slots, profiles/r06/v9_*) they take the large regime too, where every quantised
   // matrix streams its packed blocks once per step through the K-quant skinny GEMM
   // (k_qdgemm.hip, the fp16-copy values).  MS_QDGEMM selects which matrices: 1 (default) the
-  // all-Q4_K ones -- a Q6_K matrix (the Q4_K_M lm_head, half of the down / V projections) runs
-  // its fp16 copy through k_dgemm.hip, which measured faster there (its dequant is twice the
-  // VALU; r06/v11_*) --, 2 every K-quant matrix, 0 none (the fp16 copies everywhere)
+  // all-Q4_K and the all-Q5_K ones -- a Q6_K matrix (the Q4_K_M lm_head, half of the down / V
+  // projections) runs its fp16 copy through k_dgemm.hip, which measured faster there (its dequant
+  // is twice the VALU; r06/v11_*), and so does one of mixed types --, 2 every K-quant matrix, 0 none (the fp16 copies everywhere), 3 the all-Q4_K
+  // ones only (the A/B of the Q5_K form: a 128-slot Q5_K_M engine decodes 0.33-0.37 ms per step
+  // faster with its all-Q5_K matrices on packed rows, in each of four paired rounds,
+  // profiles/q5_k/qdgemm_q5_k_ab_128_slots.jsonl)
   int qlarge_min = 65;
   int qdgemm_mode = 1;
   // engines of >= lm_gemm_min slots run the large-regime lm_head (its greedy partials) on the
@@ -265,7 +272,8 @@ struct ms_engine {
     const QMat& m = q->m;
     if (m.type0 == MS_QT_Q8_0) return false;  // no packed Q8_0 skinny GEMM: the fp16 copies
     const bool q4 = m.type0 == MS_QT_Q4_K && (m.n < 2 || m.type1 == MS_QT_Q4_K) && (m.n < 3 || m.type2 == MS_QT_Q4_K);
-    return (q4 || qdgemm_mode == 2) && qdgemm_supported(M, N, K, S, epi, m);
+    const bool q5 = m.type0 == MS_QT_Q5_K && (m.n < 2 || m.type1 == MS_QT_Q5_K) && (m.n < 3 || m.type2 == MS_QT_Q5_K);
+    return (q4 || qdgemm_mode == 2 || (q5 && qdgemm_mode == 1)) && qdgemm_supported(M, N, K, S, epi, m);
   }
   bool row_groups(int B) const { return !large(B) && B > kMaxGemvRows; }
   // split count of every quantised slab projection (MS_QSPLIT; 0: as fp16): 4 measured best
@@ -702,7 +710,7 @@ struct ms_engine {
     for (const auto& q : quant_manifest)
       REQUIRE((q[2] == MS_QT_Q8_0) == (type == MS_QT_Q8_0), MS_EINVAL,
               std::string("ggml type ") + qtype_name(type) + " cannot join an engine that holds " + qtype_name(q[2]) +
-                  " tensors: an engine's quantised matrices are all Q8_0 (8) or all K-quant (Q4_K 12 / Q6_K 14)");
+                  " tensors: an engine's quantised matrices are all Q8_0 (8) or all K-quant (Q4_K 12 / Q5_K 13 / Q6_K 14)");
   }
   void note_quant(int tensor, int layer, int type) {
     for (auto& q : quant_manifest)
@@ -1161,7 +1169,7 @@ int ms_load_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t type, 
   return guarded(e, [&]() -> int {
     ms_engine& E = *e;
     REQUIRE(host != nullptr, MS_EINVAL, "null block buffer");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0 (8), Q4_K (12) or Q6_K (14)");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0 (8), Q4_K (12), Q5_K (13) or Q6_K (14)");
     HIP_OK(hipSetDevice(E.cfg.device));
     TensorDst t = tensor_dst(E, tensor, layer);
     const int64_t want = (int64_t)t.rows * (t.cols / 256) * qblock_bytes(type, false);
@@ -1188,7 +1196,7 @@ int ms_declare_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t typ
   e->drop_graphs();
   return guarded(e, [&]() -> int {
     ms_engine& E = *e;
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0 (8), Q4_K (12) or Q6_K (14)");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0 (8), Q4_K (12), Q5_K (13) or Q6_K (14)");
     HIP_OK(hipSetDevice(E.cfg.device));
     TensorDst t = tensor_dst(E, tensor, layer);
     REQUIRE(t.rows > 1 && t.cols % 256 == 0, MS_EINVAL, "not a quantisable matrix");
@@ -1234,8 +1242,10 @@ static int q4_k_m_type(int tensor, int layer, int n_layers) {
   return MS_QT_Q4_K;
 }
 
-// random blocks for every matrix: the Q4_K_M per-tensor mix (all_type 0) or one type throughout
-static int init_synthetic_quant(ms_engine* e, uint64_t seed, float scale, float jitter, int all_type) {
+// random blocks for every matrix: the Q4_K_M per-tensor mix (all_type 0), one type throughout, or
+// with base_type = Q5_K the Q5_K_M mix (Q4_K_M's with Q5_K in place of Q4_K)
+static int init_synthetic_quant(ms_engine* e, uint64_t seed, float scale, float jitter, int all_type,
+                                int base_type = MS_QT_Q4_K) {
   if (!e) return MS_EINVAL;
   e->drop_graphs();
   return guarded(e, [&]() -> int {
@@ -1255,7 +1265,8 @@ static int init_synthetic_quant(ms_engine* e, uint64_t seed, float scale, float 
     try {
       auto one = [&](int tsr, int l) {
         TensorDst t = tensor_dst(E, tsr, l);
-        const int ty = all_type ? all_type : q4_k_m_type(tsr, l, E.L);
+        int ty = all_type ? all_type : q4_k_m_type(tsr, l, E.L);
+        if (ty == MS_QT_Q4_K) ty = base_type;
         launch_synth_qblocks(ty, (uint8_t*)tmp, (int64_t)t.rows * (t.cols / 256),
                              seed ^ ((uint64_t)tsr << 56) ^ ((uint64_t)l << 48), scale, s);
         load_quant(E, tsr, l, ty, (const uint8_t*)tmp);
@@ -1284,6 +1295,10 @@ int ms_init_synthetic_q(ms_engine* e, uint64_t seed, float scale, float jitter) 
 
 int ms_init_synthetic_q8_0(ms_engine* e, uint64_t seed, float scale, float jitter) {
   return init_synthetic_quant(e, seed, scale, jitter, MS_QT_Q8_0);
+}
+
+int ms_init_synthetic_q5_k_m(ms_engine* e, uint64_t seed, float scale, float jitter) {
+  return init_synthetic_quant(e, seed, scale, jitter, 0, MS_QT_Q5_K);
 }
 
 int ms_init_synthetic(ms_engine* e, uint64_t seed, float std_, float jitter) {
@@ -2317,7 +2332,7 @@ int ms_op_residual_rmsnorm(float* x, const float* slabs, int32_t S, const void* 
 int ms_op_dequant(int32_t type, const void* blocks, int64_t n_blocks, float* out, void* stream) {
   return op_guard([&] {
     REQUIRE(blocks && out && n_blocks >= 1, MS_EINVAL, "bad dequant arguments");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K or Q6_K");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
     launch_dequant_f32(type, (const uint8_t*)blocks, n_blocks, out, (hipStream_t)stream);
   });
 }
@@ -2326,7 +2341,7 @@ int ms_op_quant_rows(int32_t type, const void* blocks, int32_t rows, int32_t K, 
                      void* packed_out, void* stream) {
   return op_guard([&] {
     REQUIRE(blocks && f16_out && rows >= 1 && K >= 256 && K % 256 == 0, MS_EINVAL, "bad quant_rows arguments");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K or Q6_K");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
     launch_quant_rows(type, (const uint8_t*)blocks, rows, K, (f16_t*)f16_out, 16, 0,
                       (uint8_t*)packed_out, 0, (hipStream_t)stream);
   });
@@ -2336,7 +2351,7 @@ int ms_op_qgemv(const void* X, int32_t type, const void* packed, void* out, int3
                 int32_t K, int32_t ldo, int32_t epi, void* stream) {
   return op_guard([&] {
     REQUIRE(X && packed && out && N >= 16, MS_EINVAL, "bad qgemv operands");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K or Q6_K");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
     REQUIRE(((epi >= 0 && epi <= 3) || epi == MS_EPI_ARGMAX) && (epi != MS_EPI_SWIGLU || N % 32 == 0),
             MS_EINVAL, "bad epilogue");
     REQUIRE(qgemv_supported(M, N, K, epi, op_rs_tiles()), MS_EINVAL,
@@ -2356,7 +2371,7 @@ int ms_op_qgemv_split(const void* X, int32_t type, const void* packed, float* sl
                       int32_t N, int32_t K, int32_t S, void* stream) {
   return op_guard([&] {
     REQUIRE(X && packed && slabs && N >= 16 && S >= 1, MS_EINVAL, "bad qgemv_split operands");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K or Q6_K");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
     REQUIRE(qgemv_split_supported(M, N, K, S, op_rs_tiles()), MS_EINVAL,
             "qgemv_split shape unsupported (M<=64, K%(256*S)==0, row-scale statistics within kRsStage and LDS)");
     QMat q{};
@@ -2370,13 +2385,36 @@ int ms_op_qgemv_split(const void* X, int32_t type, const void* packed, float* sl
   });
 }
 
+int ms_op_qgemv_resid(const void* X, int32_t type, const void* packed, float* x, void* xg_out, const void* gamma,
+                      float* ssq_out, int32_t M, int32_t N, int32_t K, int32_t rt, void* stream) {
+  return op_guard([&] {
+    REQUIRE(X && packed && x && xg_out && gamma && ssq_out && rt >= 1 && rt <= 16 && N % rt == 0, MS_EINVAL,
+            "bad qgemv_resid operands");
+    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
+    REQUIRE(qgemv_supported(M, N, K, MS_GEMV_EPI_RESID_SSQ), MS_EINVAL, "qgemv_resid shape unsupported");
+    QMat q{};
+    q.n = 1;
+    q.base0 = (const uint8_t*)packed;
+    q.row0_0 = 0;
+    q.type0 = type;
+    q.row_bytes0 = (K / 256) * qblock_bytes(type, true);
+    GemvArgs ga{};
+    ga.rt = rt;
+    ga.ssq_out = ssq_out;
+    ga.gamma = (const f16_t*)gamma;
+    ga.xg_out = (f16_t*)xg_out;
+    launch_qgemv((const f16_t*)X, q, x, M, N, K, N, MS_GEMV_EPI_RESID_SSQ, &ga, (hipStream_t)stream);
+  });
+}
+
 int ms_op_qdgemm(const void* X, int32_t type, const void* packed, void* out, int32_t M, int32_t N, int32_t K,
                  int32_t S, int32_t ldo, int32_t epi, void* stream) {
   return op_guard([&] {
     REQUIRE(X && packed && out && N >= 64 && K >= 256 && S >= 1, MS_EINVAL, "bad qdgemm operands");
     REQUIRE(type != MS_QT_Q8_0, MS_EINVAL,
-            "qdgemm has no Q8_0 form (Q8_0 engines run their fp16 copies in the large regime): Q4_K, Q6_K or F16");
-    REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q6_K || type == 1, MS_EINVAL, "ggml type must be Q4_K, Q6_K or F16");
+            "qdgemm has no Q8_0 form (Q8_0 engines run their fp16 copies in the large regime): Q4_K, Q5_K, Q6_K or F16");
+    REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q5_K || type == MS_QT_Q6_K || type == 1, MS_EINVAL,
+            "ggml type must be Q4_K, Q5_K, Q6_K or F16");
     REQUIRE(!g_op_rs.ssq || g_op_rs.tiles == 1, MS_EINVAL, "qdgemm row scale: one-tile statistics only");
     if (type == 1) {  // fp16 rows [N][K] through the same kernel
       const int e = epi == MS_EPI_ARGMAX ? MS_GEMV_EPI_ARGMAX : epi;

@@ -1,5 +1,5 @@
 // k_qdgemm.hip -- decode projections of K-quant engines at large batch: the skinny GEMM of
-// k_dgemm.hip with the weights streamed as their packed Q4_K / Q6_K rows and dequantised in
+// k_dgemm.hip with the weights streamed as their packed Q4_K / Q5_K / Q6_K rows and dequantised in
 // registers, so a Q4_K_M engine of > 64 slots reads each quantised weight ONCE per decode step
 // (1.9 GB instead of the fp16 copies' 6.4 GB; SURVEY.md §8a rows A9 / A10, BASELINE.json
 // configs[4] at configs[2]'s batch).
@@ -18,13 +18,13 @@
 //    same kernel on fp16 rows, kQdF16, runs gate/up at M = 128 in 33.7 us against 29.0 us on
 //    Q4_K; profiles/r06/v10_*);
 //  * W: one super-block (256 k) of the wave's 16 rows per ring slot, DPF super-blocks in flight
-//    (Q4_K: header + sub-blocks 0-3 / 4-7, 48 B per lane; Q6_K: four 8-B ql pieces, two 8-B qh
-//    pieces, the scales and d);
+//    (Q4_K: header + sub-blocks 0-3 / 4-7, 48 B per lane; Q5_K: the same and the lane group's 8 qh
+//    bytes; Q6_K: four 8-B ql pieces, two 8-B qh pieces, the scales and d);
 //  * MFMA column c of a super-block (v_mfma_f32_16x16x32_f16, 32 consecutive k): lane group g
 //    holds k = 32c + 8g .. +7 of its row -- the packed Q4_K layout's own order (quant_rows_kernel)
 //    and Q6_K's natural one -- and reads the same k of X;
-//  * dequant: Q4_K y = fma(d*sc, q, -(dmin*m)) (the products are exact in fp32, so this is
-//    ggml's d1*q - m1 with its single rounding), Q6_K y = fma(d*sc, q, -32 d*sc) (ggml's
+//  * dequant: Q4_K / Q5_K y = fma(d*sc, q, -(dmin*m)) (the products are exact in fp32 -- 11 + 6 + 5
+//    bits at most -- so this is ggml's d1*q - m1 with its single rounding), Q6_K y = fma(d*sc, q, -32 d*sc) (ggml's
 //    (d*sc)*(q-32)), both rounded to fp16 by v_cvt_pk_f16_f32 (RNE, as the fp16 copy);
 //  * epilogues as the skinny GEMM: fp32 split-K slabs (gridDim.y), SwiGLU on the 16-row
 //    interleaved gate/up rows, greedy argmax partials; the rows' deferred-norm scale.
@@ -41,6 +41,10 @@ __device__ __forceinline__ float qd_h2f(uint32_t h16) {
 
 struct QdQ4 {  // one packed Q4_K super-block of this lane's row: header, sub-blocks 0-3, 4-7
   uint4 h, q0, q1;
+};
+struct QdQ5 {  // one packed Q5_K super-block: Q4_K's three pieces and qh[8g .. 8g + 7]
+  uint4 h, q0, q1;
+  uint2 qh;
 };
 struct QdQ6 {  // one packed Q6_K super-block: ql pieces [k4 & 1][n], qh [n], scales, d
   uint2 ql[2][2], qh[2];
@@ -69,6 +73,12 @@ __device__ __forceinline__ void qd_fetch(QdQ4& r, const uint8_t* bp, int g) {
   r.h = qd_ld16(bp);
   r.q0 = qd_ld16(bp + 16 + 16 * g);
   r.q1 = qd_ld16(bp + 80 + 16 * g);
+}
+__device__ __forceinline__ void qd_fetch(QdQ5& r, const uint8_t* bp, int g) {
+  r.h = qd_ld16(bp);
+  r.q0 = qd_ld16(bp + 16 + 16 * g);
+  r.q1 = qd_ld16(bp + 80 + 16 * g);
+  r.qh = qd_ld8(bp + 144 + 8 * g);
 }
 __device__ __forceinline__ void qd_fetch(QdH& r, const uint8_t* bp, int g) {
 #pragma unroll
@@ -110,6 +120,20 @@ __device__ __forceinline__ f16x8 qd_dequant(const QdQ4& r, int c, int g) {
   uint32_t pk[4];
   qd_deq4(qw & 0x0F0F0F0Fu, d1, -m1, pk[0], pk[1]);
   qd_deq4((qw >> 4) & 0x0F0F0F0Fu, d1, -m1, pk[2], pk[3]);
+  return __builtin_bit_cast(f16x8, pk);
+}
+// Q5_K: Q4_K's scales and nibbles; bit c of qh[8g + i] is the fifth bit of weight 32c + 8g + i
+__device__ __forceinline__ f16x8 qd_dequant(const QdQ5& r, int c, int g) {
+  (void)g;
+  const int sh = 8 * (c & 3);
+  const uint32_t scw = c < 4 ? (r.h.y & 0x3F3F3F3Fu) : ((r.h.w & 0x0F0F0F0Fu) | ((r.h.y >> 2) & 0x30303030u));
+  const uint32_t mw = c < 4 ? (r.h.z & 0x3F3F3F3Fu) : (((r.h.w >> 4) & 0x0F0F0F0Fu) | ((r.h.z >> 2) & 0x30303030u));
+  const float d1 = __fmul_rn(qd_h2f(r.h.x), (float)((scw >> sh) & 0xFFu));
+  const float m1 = __fmul_rn(qd_h2f(r.h.x >> 16), (float)((mw >> sh) & 0xFFu));
+  const uint32_t qw = qd_word(c < 4 ? r.q0 : r.q1, c & 3);
+  uint32_t pk[4];
+  qd_deq4((qw & 0x0F0F0F0Fu) | (((r.qh.x >> c) & 0x01010101u) << 4), d1, -m1, pk[0], pk[1]);
+  qd_deq4(((qw >> 4) & 0x0F0F0F0Fu) | (((r.qh.y >> c) & 0x01010101u) << 4), d1, -m1, pk[2], pk[3]);
   return __builtin_bit_cast(f16x8, pk);
 }
 __device__ __forceinline__ f16x8 qd_dequant(const QdH& r, int c, int g) {
@@ -166,7 +190,7 @@ __device__ __forceinline__ void qd_wait_steady(int q) {
 }
 
 // vector memory instructions of one qd_fetch
-template <int QT> constexpr int kQdLoads = QT == MS_QT_Q4_K ? 3 : QT == kQdF16 ? 8 : 8;
+template <int QT> constexpr int kQdLoads = QT == MS_QT_Q4_K ? 3 : QT == MS_QT_Q5_K ? 4 : QT == kQdF16 ? 8 : 8;
 
 // the packed rows of one launch: up to three regions of one type (the fused QKV matrix's Q / K / V
 // allocations), rows [0, r1) in b0, [r1, r2) in b1, [r2, N) in b2 -- each a multiple of 64 rows,
@@ -182,6 +206,7 @@ __device__ __forceinline__ const uint8_t* qd_row(const QdSrc& s, int r) {
 
 template <int QT> struct QdRegs;
 template <> struct QdRegs<MS_QT_Q4_K> { using T = QdQ4; static constexpr int kBytes = kQ4KBytes; };
+template <> struct QdRegs<MS_QT_Q5_K> { using T = QdQ5; static constexpr int kBytes = kQ5KBytes; };
 template <> struct QdRegs<MS_QT_Q6_K> { using T = QdQ6; static constexpr int kBytes = kQ6KPacked; };
 template <> struct QdRegs<kQdF16> { using T = QdH; static constexpr int kBytes = 512; };
 
@@ -380,7 +405,7 @@ bool qdgemm_supported(int M, int N, int K, int S, int epi, const QMat& q) {
     int r0, r1, type, rb;
     const uint8_t* base;
     qd_region(q, i, N, r0, r1, base, type, rb);
-    if (r1 <= r0 || (r1 - r0) % kQdRowAlign || (type != MS_QT_Q4_K && type != MS_QT_Q6_K)) return false;
+    if (r1 <= r0 || (r1 - r0) % kQdRowAlign || (type != MS_QT_Q4_K && type != MS_QT_Q5_K && type != MS_QT_Q6_K)) return false;
     if (type != q.type0) return false;  // one launch: one type
     if (rb != (K / 256) * qblock_bytes(type, true)) return false;
   }
@@ -441,6 +466,7 @@ void launch_qdgemm(const f16_t* X, const QMat& q, void* out, int M, int N, int K
   QdSrc src{q.base0, q.n > 1 ? q.base1 : q.base0, q.n > 2 ? q.base2 : q.base0, q.n > 1 ? q.row0_1 : N,
             q.n > 2 ? q.row0_2 : N, q.row_bytes0};
   if (q.type0 == MS_QT_Q4_K) qdgemm_form<MS_QT_Q4_K>(X, src, out, M, N, K, S, ldo, epi, rs, s);
+  else if (q.type0 == MS_QT_Q5_K) qdgemm_form<MS_QT_Q5_K>(X, src, out, M, N, K, S, ldo, epi, rs, s);
   else qdgemm_form<MS_QT_Q6_K>(X, src, out, M, N, K, S, ldo, epi, rs, s);
 }
 

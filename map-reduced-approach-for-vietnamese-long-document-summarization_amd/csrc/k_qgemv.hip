@@ -41,6 +41,20 @@
 // under the exponent byte 0x64 is the fp16 1024 + (q + 128); one packed fp16 subtract of 1152
 // gives q, exact), A_b = sum_k x_k q_k, then acc = fma(d_b, A_b, acc) in fp32: the weights are
 // never rounded to fp16, out = sum_b d_b (sum_k x_k q_k).
+//
+// Q5_K (ggml type 13; the q5_K_M / q5_K_S / q4_K_S mixes) is Q4_K with a fifth bit per weight: raw
+// block {fp16 d, dmin; scales[12]; qh[32]; qs[128]} = 176 B, weight t = 32s + l has the code
+// q = nibble(t) + 16 ((qh[l] >> s) & 1) in 0..31 and y = d1*q - m1 with Q4_K's d1, m1.  Packed
+// block, 176 B, 16-B aligned:
+//   bytes 0..15     the header as is
+//   bytes 16..143   the nibbles in Q4_K's packed order (byte 16 + 64(s>>2) + 16g + 4(s&3) + i =
+//                   nib(k) | nib(k+4) << 4, k = 32s + 8g + i, i < 4)
+//   bytes 144..175  qh in its raw order: lane group g reads the 8 bytes at 144 + 8g as two dwords
+//                   Hlo, Hhi; sub-block s's fifth bits are ((H >> s) & 0x01010101) << 4, or-ed into
+//                   the low / high nibble words ahead of Q4_K's byte permute
+// The GEMV is Q4_K's, sum order included: a 5-bit code is still an exact fp16 subnormal q 2^-24.
+// Matrices with a Q5_K region run the QF = MS_QT_Q5_K instantiations (regions Q4_K / Q5_K / Q6_K
+// chosen at run time); matrices without one keep the QF = 0 instantiations unchanged.
 #include <algorithm>
 #include <cstdlib>
 
@@ -101,8 +115,24 @@ __device__ __forceinline__ float deq_q8_one(const uint8_t* b, int t) {
   return __fmul_rn(d, (float)(int)(int8_t)blk[2 + (t & 31)]);
 }
 
+// raw ggml Q5_K block: d, dmin, scales[12], qh[32], qs[128]; weight t of sub-block s = t >> 5
+__device__ __forceinline__ float deq_q5k_one(const uint8_t* b, int t) {
+  const uint4 hdr = *(const uint4*)b;
+  const float d = h2f_lo(hdr.x), dmin = h2f_lo(hdr.x >> 16);
+  const int s = t >> 5, l = t & 31, c = t >> 6;
+  int sc, m;
+  scale_min_k4(hdr, s, sc, m);
+  const uint32_t qb = b[48 + c * 32 + l];
+  const uint32_t q = ((t & 32) ? (qb >> 4) : (qb & 0xF)) + ((((uint32_t)b[16 + l] >> s) & 1u) << 4);
+  const float d1 = __fmul_rn(d, (float)sc), m1 = __fmul_rn(dmin, (float)m);
+  return __fsub_rn(__fmul_rn(d1, (float)q), m1);
+}
+
 __device__ __forceinline__ float deq_one(int type, const uint8_t* b, int t) {
-  return type == MS_QT_Q4_K ? deq_q4k_one(b, t) : type == MS_QT_Q8_0 ? deq_q8_one(b, t) : deq_q6k_one(b, t);
+  return type == MS_QT_Q4_K   ? deq_q4k_one(b, t)
+         : type == MS_QT_Q5_K ? deq_q5k_one(b, t)
+         : type == MS_QT_Q8_0 ? deq_q8_one(b, t)
+                              : deq_q6k_one(b, t);
 }
 
 __global__ __launch_bounds__(256) void dequant_f32_kernel(int type, const uint8_t* __restrict__ blocks,
@@ -152,6 +182,21 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(int type, const uint8_t
         const int k = 32 * s_ + 8 * g + i;
         q[16 + 64 * (s_ >> 2) + 16 * g + 4 * (s_ & 3) + i] = (uint8_t)(nib(k) | (nib(k + 4) << 4));
       }
+    } else if (type == MS_QT_Q5_K) {
+      // header as is, the nibbles (raw qs at byte 48) in Q4_K's packed order, qh unmoved in value:
+      // raw 16 + l -> 144 + l (file header)
+      if (t < 16) q[t] = b[t];
+      if (t < 128) {
+        const int g = t >> 5, s_ = (t >> 2) & 7, i = t & 3;
+        auto nib = [&](int k) {
+          const uint32_t qb = b[48 + (k >> 6) * 32 + (k & 31)];
+          return ((k & 63) >> 5) ? (qb >> 4) : (qb & 0xF);
+        };
+        const int k = 32 * s_ + 8 * g + i;
+        q[16 + 64 * (s_ >> 2) + 16 * g + 4 * (s_ & 3) + i] = (uint8_t)(nib(k) | (nib(k + 4) << 4));
+      } else if (t < 160) {
+        q[144 + (t - 128)] = b[16 + (t - 128)];
+      }
     } else {
       // Q6_K: same fields (qh at 128, scales at 192, d at 208, tail padded), ql regrouped by the
       // GEMV's lane group g = 2 hh + p: its low-half 16 bytes (raw hh*64 + 16p ..) at 16g and its
@@ -200,6 +245,14 @@ __global__ void synth_qblocks_kernel(int type, uint8_t* __restrict__ blocks, int
     if (type == MS_QT_Q4_K) {
       const _Float16 d = (_Float16)(u * scale / 270.f);
       const _Float16 dm = (_Float16)((float)d * 7.5f);
+      const uint16_t db = __builtin_bit_cast(uint16_t, d), dmb = __builtin_bit_cast(uint16_t, dm);
+      b[0] = db & 0xFF; b[1] = db >> 8; b[2] = dmb & 0xFF; b[3] = dmb >> 8;
+    } else if (type == MS_QT_Q5_K) {
+      // sc, m uniform on 0..63 and q on 0..31: dmin = 15.5 d centres y / d = sc q - 15.5 m, whose
+      // variance is E[sc^2] E[q^2] - (E[sc] E[q])^2 + 15.5^2 Var(m) = 434054 - 238388 + 81985, std 527;
+      // with u on [0.5, 1.5) (rms 1.041) the weights have std ~ scale for d = u scale / 548
+      const _Float16 d = (_Float16)(u * scale / 548.f);
+      const _Float16 dm = (_Float16)((float)d * 15.5f);
       const uint16_t db = __builtin_bit_cast(uint16_t, d), dmb = __builtin_bit_cast(uint16_t, dm);
       b[0] = db & 0xFF; b[1] = db >> 8; b[2] = dmb & 0xFF; b[3] = dmb >> 8;
     } else if (type == MS_QT_Q8_0) {
@@ -286,7 +339,11 @@ __device__ __forceinline__ f16x8 q8_frag(const Q8Regs& r, int s) {  // s compile
 // XM: the X source (gemv_common.h kXGlobal / kXLds / kXRegs, as in k_gemv.hip)
 // QF: 0 = K-quant regions (Q4_K / Q6_K chosen per region at run time), MS_QT_Q8_0 = a Q8_0 matrix
 // (its own instantiations: as a third run-time branch it raised the registers and the scratch of
-// every K-quant instantiation, the kernel's allocation being the largest branch's)
+// every K-quant instantiation, the kernel's allocation being the largest branch's), MS_QT_Q5_K = a
+// K-quant matrix with a Q5_K region (regions Q4_K / Q5_K / Q6_K at run time; own instantiations for
+// the same reason).  There the Q4_K body serves both 4- and 5-bit regions: a fourth load per block
+// fetches lane group g's qh bytes -- for a Q4_K region the header's first bytes, masked to zero -- so
+// the load count, and with it the counted X wait, does not depend on the region's type
 template <int QF, int MT, int NT, int EPI, int SBW, int XM, bool RS>
 __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X, QMat qm,
                                                      void* __restrict__ out, int M, int N, int K,
@@ -330,7 +387,8 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
   // Q6_K MFMA t: k = j*256 + hh*128 + (t>>1)*32 + 16p + 8(t&1)
   f16x8 xr[XR ? SBW : 1][XR ? 8 : 1][XR ? MT : 1];
   if constexpr (XR) {
-    const bool q6 = QF != MS_QT_Q8_0 && type != MS_QT_Q4_K;  // Q8_0 blocks take Q4_K's k order
+    // Q8_0 and Q5_K blocks take Q4_K's k order
+    const bool q6 = QF == MS_QT_Q5_K ? type == MS_QT_Q6_K : (QF != MS_QT_Q8_0 && type != MS_QT_Q4_K);
 #pragma unroll
     for (int j = 0; j < SBW; ++j)
 #pragma unroll
@@ -378,20 +436,25 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
           }
         }
       }
-  } else if (type == MS_QT_Q4_K) {
+  } else if (type == MS_QT_Q4_K || (QF == MS_QT_Q5_K && type == MS_QT_Q5_K)) {
+    constexpr bool Q5F = QF == MS_QT_Q5_K;
+    const bool q5 = Q5F && type == MS_QT_Q5_K;  // block-uniform
+    const int bbytes = q5 ? kQ5KBytes : kQ4KBytes;
     uint4 hq[SBW][NT], q0[SBW][NT], q1[SBW][NT];
+    uint2 q5h[Q5F ? SBW : 1][Q5F ? NT : 1];  // Q5_K: qh[8g .. 8g + 7], the fifth bits of this lane group's weights
 #pragma unroll
     for (int j = 0; j < SBW; ++j)
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
-        const uint8_t* bp = base + (size_t)(rbase + n * 16 + frw) * row_bytes + (size_t)(sbk + sb0 + j) * kQ4KBytes;
+        const uint8_t* bp = base + (size_t)(rbase + n * 16 + frw) * row_bytes + (size_t)(sbk + sb0 + j) * bbytes;
         hq[j][n] = ldw16(bp);
         q0[j][n] = ldw16(bp + 16 + 16 * g);  // sub-blocks 0-3 (quant_rows_kernel's layout)
         q1[j][n] = ldw16(bp + 80 + 16 * g);  // sub-blocks 4-7
+        if constexpr (Q5F) q5h[j][n] = *(const uint2*)(bp + (q5 ? 144 + 8 * g : 0));
       }
     if constexpr (XL) {  // the X image has landed once at most the weight loads are pending
       __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm(3 * SBW * NT));
+      __builtin_amdgcn_s_waitcnt(vmcnt_imm((Q5F ? 4 : 3) * SBW * NT));
       __builtin_amdgcn_s_barrier();  // no fence: a fence would wait for the weight loads too
     }
     typedef uint32_t u4v __attribute__((ext_vector_type(4)));
@@ -423,7 +486,12 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
             const uint4 qq = s_ < 4 ? q0[j][n] : q1[j][n];
             const int si = s_ & 3;
             const uint32_t qw = si == 0 ? qq.x : si == 1 ? qq.y : si == 2 ? qq.z : qq.w;
-            const uint32_t lo = qw & 0x0F0F0F0Fu, hi = (qw >> 4) & 0x0F0F0F0Fu;
+            uint32_t lo = qw & 0x0F0F0F0Fu, hi = (qw >> 4) & 0x0F0F0F0Fu;
+            if constexpr (Q5F) {  // bit s_ of qh[8g + i] is weight k + i's fifth bit (none in a Q4_K region)
+              const uint32_t hm = q5 ? 0x01010101u : 0u;
+              lo |= ((q5h[j][n].x >> s_) & hm) << 4;
+              hi |= ((q5h[j][n].y >> s_) & hm) << 4;
+            }
             // bytes [q, 0, q', 0] = the fp16 subnormals q * 2^-24, q' * 2^-24 (exact): weights
             // k .. k+7 in order (perm selector 0x0C is the constant byte 0)
             const u4v pk = {__builtin_amdgcn_perm(0u, lo, 0x0C010C00u), __builtin_amdgcn_perm(0u, lo, 0x0C030C02u),
@@ -891,10 +959,15 @@ static void qgemv_go(const f16_t* X, const QMat& q, void* out, int M, int N, int
     constexpr bool kRsEpi = gemv_rs_epi<EPI>();
     const bool rs = kRsEpi && ga.rs.ssq != nullptr;
     const bool q8 = q.type0 == MS_QT_Q8_0;  // an engine's matrices are all Q8_0 or all K-quant
+    // a K-quant matrix with a Q5_K region: the instantiations whose run-time branches include it
+    const bool q5 = q.type0 == MS_QT_Q5_K || (q.n > 1 && q.type1 == MS_QT_Q5_K) || (q.n > 2 && q.type2 == MS_QT_Q5_K);
 #define QLF(SBW_, XM_, RS_)                                                                                   \
     do {                                                                                                      \
       if (q8)                                                                                                 \
         MS_LAUNCH((qgemv_kernel<MS_QT_Q8_0, MT, NT, EPI, SBW_, XM_, RS_>), grid, blk, lds, s, X, q, out, M, N, K, \
+                  ldo, ro, ga);                                                                               \
+      else if (q5)                                                                                            \
+        MS_LAUNCH((qgemv_kernel<MS_QT_Q5_K, MT, NT, EPI, SBW_, XM_, RS_>), grid, blk, lds, s, X, q, out, M, N, K, \
                   ldo, ro, ga);                                                                               \
       else                                                                                                    \
         MS_LAUNCH((qgemv_kernel<0, MT, NT, EPI, SBW_, XM_, RS_>), grid, blk, lds, s, X, q, out, M, N, K, ldo, ro, \

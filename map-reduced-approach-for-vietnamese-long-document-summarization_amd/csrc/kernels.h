@@ -261,8 +261,11 @@ void launch_dgemm(const f16_t* X, const f16_t* W, void* out, int M, int N, int K
 int dgemm_kh_setting();
 
 // ---- ggml quantised weights (k_qgemv.hip): the K-quants and Q8_0
-enum { MS_QT_Q8_0 = 8, MS_QT_Q4_K = 12, MS_QT_Q6_K = 14 };  // ggml_type ids
+enum { MS_QT_Q8_0 = 8, MS_QT_Q4_K = 12, MS_QT_Q5_K = 13, MS_QT_Q6_K = 14 };  // ggml_type ids
 constexpr int kQ4KBytes = 144, kQ6KBytes = 210, kQ6KPacked = 224;
+// Q5_K: Q4_K's header and nibbles plus one high bit per weight (qh[32]); 176 B raw and packed
+// (header, the nibbles in Q4_K's packed order, then qh as is: quant_rows_kernel)
+constexpr int kQ5KBytes = 176;
 // Q8_0 counted in the K-quants' 256-weight units: 8 ggml blocks {fp16 d; int8 qs[32]} = 272 B raw,
 // and 272 B packed (the 8 scales, then the 256 quants regrouped: quant_rows_kernel)
 constexpr int kQ8Bytes = 272;
@@ -275,7 +278,7 @@ struct QMat {
   const uint8_t* base2; int row0_2, type2, row_bytes2;
 };
 // large-batch K-quant decode projections (k_qdgemm.hip): the skinny GEMM with the weights
-// streamed as packed Q4_K / Q6_K rows and dequantised in registers to their fp16-copy values;
+// streamed as packed Q4_K / Q5_K / Q6_K rows and dequantised in registers to their fp16-copy values;
 // each region launched on its own (rows % 64 == 0 per region, first region at row 0), SwiGLU /
 // argmax need one region; S > 1 = fp32 split-K slabs; K % (256 S) == 0, M <= 256
 bool qdgemm_supported(int M, int N, int K, int S, int epi, const QMat& q);
@@ -292,9 +295,12 @@ inline uint64_t smix_host(uint64_t z) {
   return z ^ (z >> 31);
 }
 __host__ __device__ inline int qblock_bytes(int type, bool packed) {
-  return type == MS_QT_Q4_K ? kQ4KBytes : type == MS_QT_Q8_0 ? kQ8Bytes : (packed ? kQ6KPacked : kQ6KBytes);
+  return type == MS_QT_Q4_K ? kQ4KBytes : type == MS_QT_Q5_K ? kQ5KBytes : type == MS_QT_Q8_0 ? kQ8Bytes
+                                        : (packed ? kQ6KPacked : kQ6KBytes);
 }
-inline bool qtype_known(int type) { return type == MS_QT_Q4_K || type == MS_QT_Q6_K || type == MS_QT_Q8_0; }
+inline bool qtype_known(int type) {
+  return type == MS_QT_Q4_K || type == MS_QT_Q5_K || type == MS_QT_Q6_K || type == MS_QT_Q8_0;
+}
 void launch_dequant_f32(int type, const uint8_t* blocks, int64_t n_blocks, float* out, hipStream_t s);
 // raw ggml rows [rows][K/256 blocks] -> fp16 rows of a fused matrix (map_row) and, if dst_q,
 // packed quantised rows at (map_row(r) - q_row_base)

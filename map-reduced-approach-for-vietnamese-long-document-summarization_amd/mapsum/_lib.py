@@ -23,7 +23,7 @@ MS_EPI_STORE_F16, MS_EPI_ADD_F32, MS_EPI_SWIGLU, MS_EPI_STORE_F32 = range(4)
 MS_EPI_ARGMAX = 5
 # the prefill GEMM dispatch the library starts with (ms_set_gemm_variant; tests restore it)
 GEMM_DEFAULT = 4
-MS_GGML_Q8_0, MS_GGML_Q4_K, MS_GGML_Q6_K = 8, 12, 14
+MS_GGML_Q8_0, MS_GGML_Q4_K, MS_GGML_Q5_K, MS_GGML_Q6_K = 8, 12, 13, 14
 # kernel classes of ms_stats.kernel_ms
 K_GEMM, K_ATTN_PREFILL, K_GEMV, K_ATTN_DECODE, K_LMHEAD, K_MISC, K_PERSIST = range(7)
 MS_DBG_KPOOL, MS_DBG_VPOOL, MS_DBG_DECODE_LOGITS, MS_DBG_DECODE_X, MS_DBG_PREFILL_LOGITS = range(5)
@@ -31,7 +31,7 @@ MS_SAMPLE_MAX_TOPK, MS_SAMPLE_MAX_WINDOW = 256, 256
 
 EXPORTED = (
     "ms_create", "ms_destroy", "ms_last_error", "ms_load_weight", "ms_init_synthetic",
-    "ms_load_weight_q", "ms_init_synthetic_q", "ms_init_synthetic_q8_0", "ms_op_dequant", "ms_op_quant_rows", "ms_op_qgemv", "ms_op_qgemv_split", "ms_op_qdgemm",
+    "ms_load_weight_q", "ms_init_synthetic_q", "ms_init_synthetic_q8_0", "ms_init_synthetic_q5_k_m", "ms_op_dequant", "ms_op_quant_rows", "ms_op_qgemv", "ms_op_qgemv_split", "ms_op_qgemv_resid", "ms_op_qdgemm",
     "ms_submit", "ms_step", "ms_poll", "ms_pending", "ms_get_stats", "ms_reset_stats",
     "ms_set_profiling", "ms_synchronize", "ms_forward", "ms_op_gemm", "ms_op_gemv_workspace",
     "ms_op_gemv", "ms_op_gemv_tuned", "ms_op_gemv_split", "ms_op_dgemm", "ms_op_residual_rmsnorm", "ms_op_rmsnorm",
@@ -107,6 +107,7 @@ def load_at(path: str, ab: bool = True) -> C.CDLL:
         "ms_load_weight_q": (i32, [vp, i32, i32, i32, vp, i64]),
         "ms_init_synthetic_q": (i32, [vp, u64, C.c_float, C.c_float]),
         "ms_init_synthetic_q8_0": (i32, [vp, u64, C.c_float, C.c_float]),
+        "ms_init_synthetic_q5_k_m": (i32, [vp, u64, C.c_float, C.c_float]),
         "ms_op_dequant": (i32, [i32, vp, i64, vp, vp]),
         "ms_op_quant_rows": (i32, [i32, vp, i32, i32, vp, vp, vp]),
         "ms_op_qgemv": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
@@ -127,6 +128,7 @@ def load_at(path: str, ab: bool = True) -> C.CDLL:
         "ms_set_eos_ids": (i32, [vp, pi32, i32]),
         "ms_op_gemv_strided": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
         "ms_op_gemv_resid": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        "ms_op_qgemv_resid": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
         "ms_op_set_row_scale": (i32, [vp, i32, i32, C.c_float]),
         "ms_op_gemm_resid": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
         "ms_gemm_resid_tiles": (i32, [i32, i32]),

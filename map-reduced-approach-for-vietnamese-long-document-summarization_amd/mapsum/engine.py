@@ -263,6 +263,10 @@ class Engine(RequestQueue):
         """Random Q8_0 blocks for every matrix, dequantised weights of std ~ scale (bench)."""
         self._chk(self.lib.ms_init_synthetic_q8_0(self.h, seed, scale, norm_jitter), "ms_init_synthetic_q8_0")
 
+    def init_synthetic_q5_k_m(self, seed: int = 2, scale: float = 0.02, norm_jitter: float = 0.0):
+        """Random Q5_K/Q6_K blocks in the Q5_K_M mix: Q4_K_M's per-tensor types, Q5_K for Q4_K (bench)."""
+        self._chk(self.lib.ms_init_synthetic_q5_k_m(self.h, seed, scale, norm_jitter), "ms_init_synthetic_q5_k_m")
+
     def load_tensor_q(self, tensor: int, layer: int, ggml_type: int, blocks: np.ndarray):
         b = np.ascontiguousarray(blocks, dtype=np.uint8)
         self._chk(self.lib.ms_load_weight_q(self.h, tensor, layer, ggml_type, b.ctypes.data, b.size),

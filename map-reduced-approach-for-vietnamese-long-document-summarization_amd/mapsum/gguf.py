@@ -10,11 +10,11 @@ llama.cpp's HF -> GGUF converter permutes the rows of attn_q / attn_k per head s
 rotary pairs are adjacent (``permute``: reshape(n_head, 2, hd/2) -> swap -> flatten).
 The kernels implement HF's rotate-half convention, so those rows are put back here.  A
 row of a quantised matrix is a whole run of blocks, so the same row permutation applies
-to Q4_K / Q6_K / Q8_0 data without dequantising.
+to Q4_K / Q5_K / Q6_K / Q8_0 data without dequantising.
 
 Supported: every matrix float (F32 / F16 / BF16, uploaded as fp16 -- the engine's type, so an
-F16 file such as llama3.2:3b-instruct-fp16 loads bit for bit), every matrix Q4_K / Q6_K (the
-Q4_K_M mix) or every matrix Q8_0 (llama3.2:3b-instruct-q8_0), with float norms.  The engine
+F16 file such as llama3.2:3b-instruct-fp16 loads bit for bit), every matrix Q4_K / Q5_K / Q6_K
+(the Q4_K_M, Q5_K_M, Q5_K_S and Q4_K_S mixes) or every matrix Q8_0 (llama3.2:3b-instruct-q8_0), with float norms.  The engine
 counts quantised rows in 256-weight units, so a Q8_0 matrix row is a multiple of 256 too.
 """
 from __future__ import annotations
@@ -25,8 +25,8 @@ import numpy as np
 
 from .weights import load_logical, load_quantized
 
-GGML_F32, GGML_F16, GGML_Q8_0, GGML_Q4_K, GGML_Q6_K, GGML_BF16 = 0, 1, 8, 12, 14, 30
-QBLOCK = {GGML_Q8_0: (32, 34), GGML_Q4_K: (256, 144), GGML_Q6_K: (256, 210)}  # weights, bytes per block
+GGML_F32, GGML_F16, GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_BF16 = 0, 1, 8, 12, 13, 14, 30
+QBLOCK = {GGML_Q8_0: (32, 34), GGML_Q4_K: (256, 144), GGML_Q5_K: (256, 176), GGML_Q6_K: (256, 210)}  # weights, bytes per block
 _FLOAT = {GGML_F32: np.float32, GGML_F16: np.float16}
 
 # value types of the metadata section
@@ -100,7 +100,7 @@ def read_gguf(path: str):
                 raise GGUFError(f"{name}: row length {dims[0]} not a multiple of {qk}")
             nbytes = n // qk * qb
         else:
-            raise GGUFError(f"{name}: ggml type {t} is not supported (F32/F16/BF16/Q8_0/Q4_K/Q6_K)")
+            raise GGUFError(f"{name}: ggml type {t} is not supported (F32/F16/BF16/Q8_0/Q4_K/Q5_K/Q6_K)")
         start = base + off
         if start + nbytes > buf.size:
             raise GGUFError(f"{name}: data runs past the end of the file")
@@ -198,7 +198,7 @@ def load_gguf(engine, path: str):
     if all(quant.values()):
         q8 = {k: v[0] == GGML_Q8_0 for k, v in mats.items()}
         if any(q8.values()) and not all(q8.values()):
-            raise GGUFError("mixed Q8_0 / K-quant (Q4_K, Q6_K) matrices are not supported")
+            raise GGUFError("mixed Q8_0 / K-quant (Q4_K, Q5_K, Q6_K) matrices are not supported")
         for k, (t, d, _) in mats.items():
             if d[0] % 256:
                 raise GGUFError(f"{k}: quantised row length {d[0]} is not a multiple of 256")

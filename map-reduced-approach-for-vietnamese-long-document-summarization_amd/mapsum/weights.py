@@ -6,7 +6,7 @@ Sources:
   * a Hugging Face Llama-3.2 checkpoint directory (``*.safetensors``; rotate-half RoPE
     convention, which is what the kernels implement) -- the real-weight path.  The
     reference pulls ``llama3.2:3b`` through Ollama (README.md:28-33); its GGUF blobs load
-    through ``mapsum.gguf.load_gguf`` (Q/K un-permutation, float, Q4_K/Q6_K or Q8_0 matrices).
+    through ``mapsum.gguf.load_gguf`` (Q/K un-permutation, float, Q4_K/Q5_K/Q6_K or Q8_0 matrices).
 The engine itself fuses Q|K|V and interleaves gate/up rows on upload (csrc/engine.cpp
 ``ms_load_weight``), so callers always pass nn.Linear [out][in] tensors.
 """
@@ -52,7 +52,7 @@ _Q_NAMES = {"embed": L.MS_T_EMBED, "lm_head": L.MS_T_LM_HEAD, "wq": L.MS_T_WQ, "
 
 
 def load_quantized(engine, qw: dict, norms: dict):
-    """Upload a quantised model -- K-quant (Q4_K / Q6_K per matrix) or Q8_0 throughout, never
+    """Upload a quantised model -- K-quant (Q4_K / Q5_K / Q6_K per matrix) or Q8_0 throughout, never
     both in one engine: qw[name] = (ggml_type, uint8 blocks) for "embed"/"lm_head" and
     qw[(layer, name)] for the per-layer matrices (rows of raw ggml blocks, GGUF order after
     Q/K un-permutation); norms = {"final_norm": f32, "layers": [{"attn_norm", "ffn_norm"}]}."""

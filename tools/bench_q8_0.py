@@ -1,5 +1,5 @@
-"""Decode cost of the three weight forms on one GPU: fp16, Q4_K_M and Q8_0 at the full
-Llama-3.2-3B shape with synthetic weights, 2048-token prompts, engines of 8 and 64 slots,
+"""Decode cost of the weight forms on one GPU: fp16, Q4_K_M and Q8_0 (and, with --dtypes, the
+Q5_K_M mix q5_k_m) at the full Llama-3.2-3B shape with synthetic weights, 2048-token prompts, engines of 8 and 64 slots,
 ignore_eos.
 
 Per slot count the three engines live side by side, every slot filled first; then runs of 64
@@ -16,6 +16,7 @@ slots) with the weight bytes a step streams, computed from the shapes, and the c
 per second as a fraction of 8 TB/s (quantised engines: of the setting named in "frac_setting").
 
 usage: python tools/bench_q8_0.py [--slots 8,64] [--prompt-len 2048] [--reps 3]
+                                  [--dtypes fp16,q4_k_m,q8_0 | fp16,q4_k_m,q5_k_m | ...]
 """
 import argparse
 import json
@@ -30,7 +31,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "map-reduced-approach-for-vietnamese-lo
 
 RUN = 64  # chained decode steps per timed run (the engine's kMaxRun)
 HBM = 8.0e12
-BITS = {"f16": 16.0, 8: 8.5, 12: 4.5, 14: 6.5625}  # per weight: 34 B / 32, 144 B / 256, 210 B / 256
+BITS = {"f16": 16.0, 8: 8.5, 12: 4.5, 13: 5.5, 14: 6.5625}  # per weight: 34 B / 32, 144, 176, 210 B / 256
 
 
 def q4_k_m_type(name, layer, n_layers):  # engine.cpp q4_k_m_type
@@ -47,7 +48,12 @@ def step_bytes(cfg, dtype):
     qd, kd = cfg.n_heads * cfg.head_dim, cfg.n_kv_heads * cfg.head_dim
     mats = {"wq": qd * cfg.hidden, "wk": kd * cfg.hidden, "wv": kd * cfg.hidden, "wo": cfg.hidden * qd,
             "w_gate": cfg.ffn * cfg.hidden, "w_up": cfg.ffn * cfg.hidden, "w_down": cfg.hidden * cfg.ffn}
-    kind = lambda n, l: "f16" if dtype == "fp16" else 8 if dtype == "q8_0" else q4_k_m_type(n, l, cfg.n_layers)  # noqa: E731
+    def kind(n, l):
+        if dtype in ("fp16", "q8_0"):
+            return "f16" if dtype == "fp16" else 8
+        t = q4_k_m_type(n, l, cfg.n_layers)
+        return 13 if dtype == "q5_k_m" and t == 12 else t  # Q5_K_M: Q5_K in place of Q4_K
+
     layers = sum(w * BITS[kind(n, l)] / 8 for l in range(cfg.n_layers) for n, w in mats.items())
     return int(layers), int(cfg.vocab * cfg.hidden * BITS[kind("lm_head", 0)] / 8)
 
@@ -98,7 +104,8 @@ def main():
     lib = L.load()
     init = {"fp16": lambda e: e.init_synthetic(seed=0, std=0.02, norm_jitter=0.0),
             "q4_k_m": lambda e: e.init_synthetic_q(seed=0, scale=0.02, norm_jitter=0.0),
-            "q8_0": lambda e: e.init_synthetic_q8_0(seed=0, scale=0.02, norm_jitter=0.0)}
+            "q8_0": lambda e: e.init_synthetic_q8_0(seed=0, scale=0.02, norm_jitter=0.0),
+            "q5_k_m": lambda e: e.init_synthetic_q5_k_m(seed=0, scale=0.02, norm_jitter=0.0)}
     dtypes = args.dtypes.split(",")
     for slots in [int(s) for s in args.slots.split(",")]:
         rng = np.random.default_rng(slots)
