@@ -254,6 +254,10 @@ int ms_debug_pk_stamps(uint64_t* out, int32_t n);
    (entry, XCC / HW id, prologue, per-wave S and P.V done, partial stored), recorded only under
    MS_A2_STAMPS=1 (tools/a2_stamps.py) */
 int ms_debug_a2_stamps(uint64_t* out, int32_t n);
+/* diagnostic: the fp16 decode GEMV's per-block phase stamps of its latest stamped launch,
+   [1024][32] (k_gemv.hip lists the slots), recorded only under MS_GEMV_STAMPS=1
+   (tools/gemv_stamps.py) */
+int ms_debug_gemv_stamps(uint64_t* out, int32_t n);
 
 /* ---- parity probe (tests): one prompt through the prefill path -------------- */
 /* hidden_out: [n][hidden] fp32 residual after `n_layers_run` layers (or NULL);
@@ -298,6 +302,13 @@ int ms_gemm_resid_tiles(int32_t M, int32_t N);
    3 = 256x256 on 4 waves, 4 = 3 for the stored epilogues and 2 for the residual one; every
    variant gives the same bits) */
 int ms_set_gemm_variant(int32_t variant);
+/* tuning/test hook: issue order of the fp16 decode GEMVs that stage X by LDS DMA: 0 = the X
+   requests ahead of the weight stream, 1 = the first weight step ahead of them, 2 = that with
+   per-wave X slices (no X barrier), -1 = the library's per-shape choice (MS_GEMV_ORDER_DEFAULT,
+   what it starts with).  Every order gives the same bits.  An engine launches whatever is set
+   when it captures its decode graphs. */
+#define MS_GEMV_ORDER_DEFAULT (-1)
+int ms_set_gemv_order(int32_t order);
 /* tuning/test hook: the quantised GEMVs that have a grid-stride two-stage form (the Q6_K and the
    Q8_0 lm_head argmax, the Q4_K gate/up SwiGLU) all take it (1) or all run one-tile blocks (0);
    the two give bit-identical outputs.  The library starts with the two K-quant forms on and the
@@ -329,7 +340,7 @@ int ms_op_gemv_tuned(const void* X, const void* W, void* out, int32_t M, int32_t
 int ms_op_gemv_strided(const void* X, const void* W, void* out, int32_t M, int32_t N, int32_t K,
                        int32_t ldk, int32_t ldo, int32_t epilogue, void* stream);
 /* decode O / down with the residual update fused (the engine's small-regime layer): x fp32
-   [M][N] += X . W^T on rt-row tiles (N % rt == 0, tiles = N / rt <= 256), and the input of the
+   [M][N] += X . W^T on rt-row tiles (tiles = ceil(N / rt) <= 256; the last may be ragged), and the input of the
    next normalised projection: xg_out fp16 [M][N] = f16(x * gamma * 2^-4), ssq_out fp32 [tiles][M] =
    per-tile sums of the new x^2 (its deferred RMSNorm statistics, see ms_op_set_row_scale) */
 int ms_op_gemv_resid(const void* X, const void* W, float* x, void* xg_out, const void* gamma,

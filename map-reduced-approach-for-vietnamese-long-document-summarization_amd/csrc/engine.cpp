@@ -2217,6 +2217,18 @@ int ms_set_gemm_variant(int32_t v) {
   return MS_OK;
 }
 
+int ms_set_gemv_order(int32_t order) {
+  if (order < -1 || order > 2) return MS_EINVAL;
+  set_gemv_order(order);
+  return MS_OK;
+}
+
+int ms_debug_gemv_stamps(uint64_t* out, int32_t n) {
+  if (!out || n < 0) return MS_EINVAL;
+  ms::gemv_stamps(reinterpret_cast<unsigned long long*>(out), n);
+  return MS_OK;
+}
+
 int ms_set_attn_tuning(int32_t combine_grp, int32_t order) {
   if (combine_grp < 0 || combine_grp > 1 || (order != 0 && order != 3)) return MS_EINVAL;
   set_attn_tuning(combine_grp, order);
@@ -2280,7 +2292,8 @@ int ms_op_gemv_strided(const void* X, const void* W, void* out, int32_t M, int32
 int ms_op_gemv_resid(const void* X, const void* W, float* x, void* xg_out, const void* gamma,
                      float* ssq_out, int32_t M, int32_t N, int32_t K, int32_t rt, void* stream) {
   return op_guard([&] {
-    REQUIRE(X && W && x && xg_out && gamma && ssq_out && rt >= 1 && rt <= 16 && N % rt == 0, MS_EINVAL,
+    // (a ragged last tile is fine: its rows are clamped on load and masked in the epilogue)
+    REQUIRE(X && W && x && xg_out && gamma && ssq_out && rt >= 1 && rt <= 16 && N >= 1, MS_EINVAL,
             "bad gemv_resid operands");
     REQUIRE(gemv_supported(M, N, K, MS_GEMV_EPI_RESID_SSQ), MS_EINVAL, "gemv_resid shape unsupported");
     GemvArgs ga{};

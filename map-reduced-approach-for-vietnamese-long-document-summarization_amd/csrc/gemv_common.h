@@ -27,7 +27,8 @@ __device__ __forceinline__ void lds_sync() {
 // X rows [M][K] fp16 (row stride ldx elements) -> LDS image of M rows x 2K bytes, 16-B
 // chunk c of row r stored at chunk c ^ (r & 7) (the rows of an MFMA fragment read land on
 // different bank groups).  Copied by LDS DMA (global_load_lds, 1 KiB per wave instruction)
-// and issued BEFORE the weight stream: vmcnt retires loads in issue order, so X loaded
+// and issued BEFORE the weight stream (k_gemv.hip's weight-first orders let one weight step per
+// wave pass ahead of it, which the first MFMA needs anyway): vmcnt retires loads in issue order, so X loaded
 // after the weights would hold the image -- and every wave of the block, at the barrier --
 // until the block's whole weight stream had landed, serialising all the dequant / MFMA work
 // behind the memory phase; the DMA needs no registers (a register copy cost the GEMVs
@@ -48,8 +49,39 @@ __device__ __forceinline__ void gemv_dma_x(char* smem, const f16_t* __restrict__
   }
 }
 
+// Per-wave X slices (kXWave, k_gemv.hip): wave w multiplies only k in [kbeg, kbeg + 64 U) of X, so
+// it copies just that slice into an LDS region of its own -- per 64-k step ceil(M / 8) DMA pieces of
+// 8 rows x 128 B -- waits on its own vmcnt and needs no block barrier in front of its MFMAs.
+// The 16-B chunk c of row r is stored at chunk c ^ xw_swz(r) of its 128-B row (the swizzle sits
+// on the per-lane SOURCE address, the DMA's LDS side is lane-linear): the rows and chunks that one
+// 16-lane group of a ds_read_b128 fragment read touches then fall on 16 different bank groups.
+__host__ __device__ inline size_t gemv_xw_lds_bytes(int M, int K) { return (size_t)((M + 7) >> 3) * K * 16; }
+__device__ __forceinline__ int xw_swz(int r) {
+  const int t = r >> 1;
+  return ((((t >> 1) ^ (t >> 2)) & 1) << 2) | ((t & 1) << 1) | ((t >> 2) & 1);
+}
+// byte offset of chunk c (0..7) of row r, step u, inside a wave's region (mp = pieces per step)
+__device__ __forceinline__ int xw_lds(int r, int u, int c, int mp) {
+  return (u * mp * 8 + r) * 128 + ((c ^ xw_swz(r)) << 4);
+}
+template <int U>
+__device__ __forceinline__ void gemv_dma_x_wave(char* smem, const f16_t* __restrict__ X, int M, int ldx,
+                                                int kbeg) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, mp = (M + 7) >> 3;
+  char* base = smem + (size_t)wave * U * mp * 1024;
+#pragma unroll 1  // one source address live at a time: the weight stages fill the gate/up GEMV's 64 VGPRs
+  for (int j = 0; j < mp; ++j) {
+    const int r = j * 8 + (lane >> 3);
+    const f16_t* src = X + (size_t)min(r, M - 1) * ldx + kbeg + (((lane & 7) ^ xw_swz(r)) << 3);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      __builtin_amdgcn_global_load_lds((const void*)(src + u * 64), (LDS_AS void*)(base + (size_t)(u * mp + j) * 1024),
+                                       16, 0, 0);
+  }
+}
+
 // where a decode GEMV's MFMA takes its X fragments from (k_gemv.hip / k_qgemv.hip)
-enum { kXGlobal = 0, kXLds = 1, kXRegs = 2 };
+enum { kXGlobal = 0, kXLds = 1, kXRegs = 2, kXWave = 3 };
 
 // The deferred RMSNorm scale of a GEMV block's output rows (kernels.h RowScale), compiled only
 // into the instantiations that take one (template RS; the rest carry none of this code).  The
@@ -176,7 +208,9 @@ __device__ __forceinline__ void gemv_elem(int e, int NT, int n0, int& row, int& 
   c = l & 15;
   col = n0 + (mn % NT) * 16 + c;
 }
-template <int EPI>
+// RAW: g keeps the gain's fp16 bits (resid_gain converts them once the weight stream is under way):
+// converting here makes the wave wait for both loads before it issues anything else
+template <int EPI, bool RAW = false>
 __device__ __forceinline__ ResidPre resid_prefetch(int M, int N, int ldo, const void* out, int n0,
                                                    const GemvArgs& ga) {
   ResidPre p{0.f, 0.f};
@@ -187,11 +221,15 @@ __device__ __forceinline__ ResidPre resid_prefetch(int M, int N, int ldo, const 
       gemv_elem(threadIdx.x, 1, n0, row, col, c);
       if (row < M && c < rtv && col < N) {
         p.x = ((const float*)out)[(size_t)row * ldo + col];
-        if (ga.xg_out) p.g = h2f(ga.gamma[col]);
+        if (ga.xg_out) p.g = RAW ? __uint_as_float((unsigned)ga.gamma[col]) : h2f(ga.gamma[col]);
       }
     }
   }
   return p;
+}
+__device__ __forceinline__ void resid_gain(ResidPre& p) {
+  asm volatile("" : "+v"(p.g));  // opaque: else the conversion folds back into the load's block
+  p.g = h2f((f16_t)__float_as_uint(p.g));
 }
 
 // RS: the block's output rows carry a deferred-norm scale (ga.rs, rs_begin); RS_DONE: the
@@ -201,7 +239,7 @@ template <int MT, int NT, int EPI, bool RS = false, bool RS_DONE = false, bool R
 __device__ __forceinline__ void gemv_finish(const f32x4 (&acc)[MT][NT], char* smem, size_t rinv_off,
                                             int M, int N, int ldo, void* __restrict__ out, int n0,
                                             const GemvArgs& ga, const ResidPre& pre = ResidPre{0.f, 0.f},
-                                            float rs_direct = 0.f) {
+                                            float rs_direct = 0.f, unsigned long long* t_red = nullptr) {
   constexpr int ELEMS = MT * NT * 256;  // floats per wave result [mt][nt][lane][j]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* rinv = (const float*)(smem + rinv_off);
@@ -214,6 +252,7 @@ __device__ __forceinline__ void gemv_finish(const f32x4 (&acc)[MT][NT], char* sm
 #pragma unroll
     for (int n = 0; n < NT; ++n)
       *(f32x4*)&red[wave * ELEMS + ((m * NT + n) * 64 + lane) * 4] = acc[m][n];
+  if (t_red) *t_red = __builtin_amdgcn_s_memrealtime();  // timeline stamp (k_gemv.hip, diagnostic builds)
   __syncthreads();
   gemv_epilogue<MT, NT, EPI, RS>(red, rinv, M, N, ldo, out, n0, ga, pre);
 }

@@ -237,6 +237,12 @@ void launch_argmax_partials(const void* partials, int rows, int tiles, int32_t* 
 bool residual_rmsnorm_supported(int S, int H);
 void launch_residual_rmsnorm(float* x, const float* slabs, int S, const f16_t* w, f16_t* y,
                              float* ssq, int rows, int H, hipStream_t s);
+// issue order of the DMA-staged decode GEMVs: 0 = X requests ahead of the weight stream, 1 = the
+// first weight step ahead of them, 2 = that with per-wave X slices and no X barrier; -1 (the
+// library's start) = the per-shape choice of k_gemv.hip.  Every order gives the same bits.
+void set_gemv_order(int v);
+// the fp16 decode GEMV's per-block phase stamps of its latest stamped launch (MS_GEMV_STAMPS=1), [1024][32]
+void gemv_stamps(unsigned long long* host, int n);
 size_t gemv_workspace_bytes(int M, int N, int K);
 // rs_tiles > 0: the call carries deferred-norm statistics of that many tiles (RowScale), which
 // the staged-partials LDS and kRsStage must also fit

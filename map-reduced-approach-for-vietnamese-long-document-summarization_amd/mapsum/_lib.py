@@ -23,6 +23,8 @@ MS_EPI_STORE_F16, MS_EPI_ADD_F32, MS_EPI_SWIGLU, MS_EPI_STORE_F32 = range(4)
 MS_EPI_ARGMAX = 5
 # the prefill GEMM dispatch the library starts with (ms_set_gemm_variant; tests restore it)
 GEMM_DEFAULT = 4
+# the decode GEMV issue order the library starts with: its per-shape choice (ms_set_gemv_order)
+GEMV_ORDER_DEFAULT = -1
 MS_GGML_Q8_0, MS_GGML_Q4_K, MS_GGML_Q5_K, MS_GGML_Q6_K = 8, 12, 13, 14
 # kernel classes of ms_stats.kernel_ms
 K_GEMM, K_ATTN_PREFILL, K_GEMV, K_ATTN_DECODE, K_LMHEAD, K_MISC, K_PERSIST = range(7)
@@ -40,7 +42,7 @@ EXPORTED = (
     "ms_forward_packed", "ms_submit_forced", "ms_set_eos_ids", "ms_op_gemv_strided",
     "ms_op_gemv_resid", "ms_op_set_row_scale", "ms_op_gemm_resid", "ms_gemm_resid_tiles",
     "ms_trace_push", "ms_trace_pop", "ms_debug_a2_stamps", "ms_set_persist", "ms_debug_read", "ms_debug_pk_stamps",
-    "ms_submit_sampled", "ms_op_sample",
+    "ms_submit_sampled", "ms_op_sample", "ms_set_gemv_order", "ms_debug_gemv_stamps",
 )
 
 
@@ -142,6 +144,7 @@ def load_at(path: str, ab: bool = True) -> C.CDLL:
         "ms_op_residual_rmsnorm": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, vp]),
         "ms_op_rmsnorm": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
         "ms_set_gemm_variant": (i32, [i32]),
+        "ms_set_gemv_order": (i32, [i32]),
         "ms_set_qgemv_gs": (i32, [i32]),
         "ms_set_attn_tuning": (i32, [i32, i32]),
         "ms_set_dgemm_kh": (i32, [i32]),
@@ -157,6 +160,7 @@ def load_at(path: str, ab: bool = True) -> C.CDLL:
         "ms_debug_read": (i32, [vp, i32, i64, vp, i64]),
         "ms_debug_pk_stamps": (i32, [vp, i32]),
         "ms_debug_a2_stamps": (i32, [vp, i32]),
+        "ms_debug_gemv_stamps": (i32, [vp, i32]),
     }
     for name, (res, args) in sig.items():
         if ab and not hasattr(lib, name):  # an A/B build may predate the newest op hooks
