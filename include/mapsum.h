@@ -85,23 +85,26 @@ typedef struct ms_config {
   /* engine */
   int32_t device;               /* HIP device ordinal                         */
   int32_t max_batch;            /* sequences in flight (<= 1024).  Also fixes the
-                                   engine's decode arithmetic (fp16 weights:
+                                   engine's decode arithmetic, ranked in ONE place,
+                                   pick_form of csrc/decode_forms.h (the table:
+                                   DESIGN.md section 5, pinned on the CPU by
+                                   tests/native/decode_forms.cpp).  fp16 weights:
                                    1-16 residual-fused GEMV, 17-23 split GEMV +
                                    residual_rmsnorm, 24-95 skinny GEMM, 96-191
                                    + the lm_head on the 128x128 GEMM tile,
-                                   >= 192 + the fp16-rows K-quant GEMM form;
+                                   >= 192 the skinny GEMM's fp16-rows form with
+                                   QKV / down split 3 / 4;
                                    K-quant: 1-16 residual-fused Q-GEMV, 17-64
-                                   split Q-GEMV + residual_rmsnorm, >= 65 the
+                                   split-4 Q-GEMV + residual_rmsnorm, >= 65 the
                                    K-quant skinny GEMM (all-Q4_K and all-Q5_K
-                                   matrices; the others their fp16 copies),
-                                   lm_head tile from 96;
-                                   Q8_0: 1-16 residual-fused Q-GEMV, 17-64 split
-                                   Q-GEMV + residual_rmsnorm in row groups of
-                                   <= 64 (the exact d*q weights), >= 65 the fp16
-                                   copies on the skinny GEMM, lm_head tile from
-                                   96); results
-                                   are batch-invariant inside one engine, not
-                                   across these boundaries */
+                                   matrices; Q6_K and mixed ones their fp16
+                                   copies on the skinny GEMM), lm_head tile from
+                                   96, the 3 / 4 splits from 192;
+                                   Q8_0: as K-quant up to 64 (the exact d*q
+                                   weights), >= 65 every matrix's fp16 copy on
+                                   the skinny GEMM, lm_head tile from 96.
+                                   Results are batch-invariant inside one engine,
+                                   not across these boundaries                   */
   int32_t max_ctx;              /* prompt + generated tokens per sequence     */
   int32_t max_prefill_tokens;   /* packed prompt tokens per prefill pass      */
   int32_t n_pages;              /* KV pages of 64 tokens; 0 = enough for all  */
@@ -235,8 +238,9 @@ int ms_trace_push(const char* name);
 int ms_trace_pop(void);
 int ms_synchronize(ms_engine* e);
 /* the decode step's layers as ONE persistent launch (k_persist.hip; engines of <= 8 slots on
-   fp16 Llama-3.2-3B weights, bit-identical to the per-layer launches): on (1, the default, also
-   MS_PERSIST) or off (0).  Returns 1 when this engine supports it, 0 when it never runs it. */
+   fp16 Llama-3.2-3B weights, bit-identical to the per-layer launches).  Opt-in: an engine starts
+   with it off (0) unless MS_PERSIST=1 is set at ms_create; 1 turns it on (it measured slower than
+   the launches).  Returns 1 when this engine supports it, 0 when it never runs it. */
 int ms_set_persist(ms_engine* e, int32_t on);
 /* test hook: copy `bytes` from byte `offset` of an engine buffer to host memory (after the
    engine's streams are idle) */

@@ -19,15 +19,12 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <array>
-#include <functional>
 #include <map>
 #include <tuple>
 #include <memory>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -38,14 +35,12 @@ static inline int roctxRangePushA(const char*) { return 0; }
 static inline int roctxRangePop() { return 0; }
 #endif
 
-#include "kernels.h"
-#include "mapsum.h"
+#include "decode_forms.h"
+#include "internal.h"
 
 using namespace ms;
 
 namespace {
-
-thread_local std::string g_last_error;
 
 // roctx ranges around the scheduler's phases (SURVEY.md §5 tracing): rocprofv3 --marker-trace
 // separates admission, the packed prefill and each decode run on the timeline (host ranges;
@@ -56,23 +51,6 @@ struct TraceRange {
   TraceRange(const TraceRange&) = delete;
   TraceRange& operator=(const TraceRange&) = delete;
 };
-
-struct MsError : std::runtime_error {
-  int code;
-  MsError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-#define HIP_OK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      throw MsError(MS_EIO, std::string(#expr) + ": " + hipGetErrorString(e_));             \
-  } while (0)
-
-#define REQUIRE(cond, code, msg)                      \
-  do {                                                \
-    if (!(cond)) throw MsError((code), (msg));        \
-  } while (0)
 
 const char* qtype_name(int type) {
   return type == MS_QT_Q8_0   ? "Q8_0 (8)"
@@ -108,16 +86,6 @@ struct Layer {
          *wgu = nullptr, *wdown = nullptr;
 };
 
-// Quantised (ggml K-quant) copy of one fused matrix for the decode GEMV; `need` = the
-// logical tensors that must all be loaded quantised before decode uses it.
-struct QSlot {
-  QMat m{};
-  size_t bytes[3] = {0, 0, 0};  // device bytes of each region (weight broadcast)
-  uint32_t loaded = 0, need = 0;
-  bool ready() const { return need != 0 && loaded == need; }
-};
-enum { QS_QKV = 0, QS_O = 1, QS_GU = 2, QS_DOWN = 3 };
-
 }  // namespace
 
 struct ms_engine {
@@ -148,54 +116,21 @@ struct ms_engine {
   // decode O / down projections: split-K partial slabs [S][B][H] fp32, folded into the
   // residual by the next residual_rmsnorm launch (pending_split = S of the unfolded slabs)
   float* slabs = nullptr;
-  int split_qkv = 6, split_o = 6, split_down = 4, pending_split = 0;
-  // large-batch regime (BASELINE configs[2]): QKV / O / down / gate-up / lm_head on the skinny
-  // GEMM (k_dgemm.hip, split 6 / 4 / 8 / 1 / 1).  The regime is chosen per ENGINE, from its
-  // max_batch (>= dgemm_min), never from the rows of one step: every step of an engine then
-  // runs one arithmetic whatever the number of sequences in flight (admission ramps, tails,
-  // a chunk alone), so a chunk's summary never depends on its companions.  The crossover:
-  // at M = 16 the GEMV and the skinny GEMM tie over a layer's four projections, at M = 32
-  // the skinny GEMM takes 30 % less (profiles/r02/v7_dgemm_lds_sync_ab.txt).
-  int dgemm_min = 24, dsplit_qkv = 6, dsplit_o = 4, dsplit_down = 8;
-  // gate/up skinny-GEMM block form (k_dgemm.hip kh), fixed per engine like the regime: the
-  // library setting (2, the default: k split over the two wave groups of an 8-wave block;
-  // 41.4 -> 34.9 us at M = 128, profiles/r05/v20_*) for engines of <= 128 slots; the split
-  // projections and the lm_head keep the 4-wave block (as fast or faster there)
-  int dgemm_kh = 1;
-  // weight-row groups per skinny-GEMM block (k_dgemm.hip wn) for launches of <= 128 rows: the
-  // 128-row block for QKV, down and the lm_head (down 22.3 -> 20.4 us, lm_head 262 -> 241 us at
-  // M = 128, profiles/r05/v21_*), 64 rows for O (15.6 vs 12.9 us at its split 4); bit-identical
-  int dwn_qkv = 8, dwn_o = 4, dwn_down = 8, dwn_lm = 8;
-  bool large_engine = false;
-  int attn_ppw = 2;  // decode attention pages per wave, fixed per engine (k_attn.hip)
-  // decode attention with one page per wave (k_attn.hip v2, MS_ATTN_V2), attn_ppb waves / pages
-  // per block, fixed per engine like attn_ppw
-  bool attn_v2 = false;
-  int attn_ppb = 9;
-  // v2's splits merged inside the launch by the last block of each group (MS_ATTN_TICKET)
-  bool attn_ticket = false;
+  int pending_split = 0;
+  // every regime / tuning choice (resolve_settings at ms_create; later only has_quant and persist change)
+  DecodeSettings S;
   unsigned* attn_cnt = nullptr;  // [max_batch * Hk] arrival counters, zero between launches
   bool attn2_ok(int B, int max_len) const {
-    return attn_v2 && slot_major && attn_decode2_supported(B, Hq, Hk, max_len, attn_ppb);
+    return S.attn_v2 && slot_major && attn_decode2_supported(B, Hq, Hk, max_len, S.attn_ppb);
   }
   void attn_decode(const DecodeQKV& qa, const KVView& kv, const DecodeAttnArgs& da) {
     prof_begin(K_ATTN_DECODE);
     if (attn2_ok(da.B, da.max_len))
-      launch_attn_decode2(qa, attn, Hq, Hk, kv, da, attn_ws, attn_ppb, stream, attn_ticket ? attn_cnt : nullptr);
+      launch_attn_decode2(qa, attn, Hq, Hk, kv, da, attn_ws, S.attn_ppb, stream, S.attn_ticket ? attn_cnt : nullptr);
     else
       launch_attn_decode(qa, attn, Hq, Hk, kv, da, attn_ws, stream);
     prof_end(K_ATTN_DECODE);
   }
-  // Residual-fused decode (small-regime engines, fp16 O / down): O and down run unsplit on
-  // resid_rt-row tiles (3072 / 12 = 256 workgroups, one per CU) and their epilogue adds into
-  // the fp32 residual and emits the next projection's input itself -- xb = f16(x * g_next)
-  // and per-tile sums of x^2 (ssq [256][B]) -- so the decode layer has no residual_rmsnorm
-  // launch: the deferred RMSNorm (kernels.h RowScale) scales the rows of the QKV / gate-up /
-  // lm_head outputs instead.  Chosen per engine (MS_RESID_FUSED=0: split-K slabs + norm
-  // launches, the large-regime form; K-quant engines take it too, below: qresid).
-  bool resid_fuse = true, has_quant = false;
-  // decode_tail_kernel: the step's greedy ids, argument advance and next embedding in one launch
-  bool tail_fuse = true;
   // The decode step's layers as ONE persistent launch (k_persist.hip, MS_PERSIST / ms_set_persist;
   // off by default until it measures faster than the launches):
   // engines of <= 8 slots on fp16 Llama-3.2-3B weights in the residual-fused / v2-attention
@@ -203,7 +138,7 @@ struct ms_engine {
   // ms_create) and per run (no profiling mask, no prefill overlap: every workgroup must be
   // resident); a hand-off timeout sets pk_err_d, and decode_run recomputes the run with the
   // launches and turns the persistent step off for the engine.
-  bool persist = false, persist_ok = false, pk_used = false;
+  bool persist_ok = false, pk_used = false;
   int n_cu = 0, nsplit_ws = 1;
   unsigned* pk_sync = nullptr;   // [persist_sync_words(L)] zero between launches
   unsigned* pk_err_d = nullptr;  // timeout flag
@@ -216,73 +151,9 @@ struct ms_engine {
   char* pk_packed = nullptr;
   mutable bool pk_packed_ok = false;
   bool persist_on(int B) const {
-    return persist && persist_ok && !overlap && B >= 1 && B <= cfg.max_batch && !has_quant &&
-           attn2_ok(B, max_pages * kPage) && attn_slabs && resid_fused(nullptr) && split_qkv == 6;
+    return S.persist && persist_ok && !S.overlap && B >= 1 && B <= cfg.max_batch && !S.has_quant &&
+           attn2_ok(B, max_pages * kPage) && S.attn_slabs && S.resid_fused(nullptr) && S.split_qkv == 6;
   }
-  int resid_rt = 12;
-  // K-quant O / down with the same epilogue (the Q-GEMV on resid_rt-row tiles; MS_QRESID=0:
-  // split-K 4 + residual_rmsnorm): 1.785 vs 1.794 ms per Q4_K_M decode step -- O 5.8 vs 4.8 +
-  // 4.7 us, down 12.8 vs 8.8 + 4.7 us, the gate/up folding 256 statistics tiles +0.9 us
-  // (profiles/r04/v31_*; round 3 measured it even before the Q-GEMV rewrites)
-  bool qresid = true;
-  // the K-quant GEMVs this regime launches support its shapes (ms_create: RESID_SSQ on O / down
-  // and the gate/up SwiGLU folding 256 statistics tiles); the launchers return silently on an
-  // unsupported shape, so an engine whose quantised shapes fall outside the Q plan takes split-K
-  // + residual_rmsnorm instead of skipping the residual update
-  bool qresid_ok = true;
-  bool resid_fused(const QSlot* q) const {
-    if (!resid_fuse || large_engine) return false;
-    if (has_quant && !qresid_ok) return false;
-    return !(q && q->ready()) || qresid;
-  }
-  // the large-batch arithmetic (skinny GEMM) for engines of >= dgemm_min slots.  Engines with
-  // K-quant weights keep the exact Q4_K / Q6_K GEMV up to qlarge_min - 1 slots (in row groups of
-  // <= kMaxGemvRows above 64: a row's sum order does not depend on its group); from qlarge_min
-  // (MS_QLARGE_MIN, default 65: the row groups' weight re-streams cost Q4_K_M 18.2 ms per decode
-  // step at 128 slots, profiles/r06/v9_*) they take the large regime too, where every quantised
-  // matrix streams its packed blocks once per step through the K-quant skinny GEMM
-  // (k_qdgemm.hip, the fp16-copy values).  MS_QDGEMM selects which matrices: 1 (default) the
-  // all-Q4_K and the all-Q5_K ones -- a Q6_K matrix (the Q4_K_M lm_head, half of the down / V
-  // projections) runs its fp16 copy through k_dgemm.hip, which measured faster there (its dequant
-  // is twice the VALU; r06/v11_*), and so does one of mixed types --, 2 every K-quant matrix, 0 none (the fp16 copies everywhere), 3 the all-Q4_K
-  // ones only (the A/B of the Q5_K form: a 128-slot Q5_K_M engine decodes 0.33-0.37 ms per step
-  // faster with its all-Q5_K matrices on packed rows, in each of four paired rounds,
-  // profiles/q5_k/qdgemm_q5_k_ab_128_slots.jsonl)
-  int qlarge_min = 65;
-  int qdgemm_mode = 1;
-  // engines of >= lm_gemm_min slots run the large-regime lm_head (its greedy partials) on the
-  // prefill GEMM's 128x128 tile (k_gemm.hip gemm_kernel, ~1000 blocks of 128 vocabulary rows)
-  // instead of the skinny GEMM: 169 vs 252 us at 128 rows, 276 vs 429 at 256
-  // (profiles/r06/v21_rows_dgemm_vs_gemm128.txt).  Per engine, so its arithmetic never changes
-  // with the rows of a step; MS_LM_GEMM_MIN (0 = never) for A/B.
-  int lm_gemm_min = 96;
-  // fp16 engines of >= qdf_min slots (16-row-tile launches of up to 256 rows) run their skinny
-  // GEMMs on k_qdgemm.hip's fp16-rows form (activations by LDS DMA three steps ahead) with
-  // QKV / down split 3 / 4 instead of 6 / 8: at 256 rows gate/up 57.3 -> 50.4 us, QKV 30.2 ->
-  // 22.6, down 43.3 -> 34.5, O 19.8 -> 19.2 (profiles/r06/v22_*).  Per engine (MS_QDF_MIN, 0 =
-  // never): below it the tested 24-128-slot arithmetic is unchanged.
-  int qdf_min = 192;
-  bool qdf(int M, int N, int K, int S, int epi) const {
-    return !has_quant && qdf_min > 0 && cfg.max_batch >= qdf_min && qdgemm_f16_supported(M, N, K, S, epi);
-  }
-  bool large(int) const { return large_engine && (!has_quant || cfg.max_batch >= qlarge_min); }
-  // the K-quant skinny GEMM for this matrix (large regime)
-  bool qd(const QSlot* q, int M, int N, int K, int S, int epi) const {
-    if (!qdgemm_mode || !q || !q->ready()) return false;
-    const QMat& m = q->m;
-    if (m.type0 == MS_QT_Q8_0) return false;  // no packed Q8_0 skinny GEMM: the fp16 copies
-    const bool q4 = m.type0 == MS_QT_Q4_K && (m.n < 2 || m.type1 == MS_QT_Q4_K) && (m.n < 3 || m.type2 == MS_QT_Q4_K);
-    const bool q5 = m.type0 == MS_QT_Q5_K && (m.n < 2 || m.type1 == MS_QT_Q5_K) && (m.n < 3 || m.type2 == MS_QT_Q5_K);
-    return (q4 || qdgemm_mode == 2 || (q5 && qdgemm_mode == 1)) && qdgemm_supported(M, N, K, S, epi, m);
-  }
-  bool row_groups(int B) const { return !large(B) && B > kMaxGemvRows; }
-  // split count of every quantised slab projection (MS_QSPLIT; 0: as fp16): 4 measured best
-  // for Q4_K_M at B = 8 -- 1.878 vs 1.900 ms/step with the fp16 splits (6 / 6 / 4), 2 / 3 / 8
-  // slower (profiles/r02/v27_qsplit_sweep_q4_k_m.txt)
-  int qsplit = 4;
-  // decode attention variant (tuning): q/k/v from QKV split slabs (else the GEMV RoPE
-  // epilogue, B <= 16)
-  bool attn_slabs = true;
   // the deferred RMSNorm scale of the rows now in xb (set by whoever wrote xb)
   RowScale cur_rs{};
   int32_t* args_d = nullptr;
@@ -298,7 +169,7 @@ struct ms_engine {
   // interfere -- the prefill GEMMs and the decode step's short launches share every CU, so
   // prefill took +28 % and a decode step +23 % -- and the whole job was 8 % SLOWER with a
   // 16-step run under each prefill (2.6 % slower with one-step runs), natural EOS or not.  So
-  // the phases run one after the other by default; MS_OVERLAP=1 turns the overlap on.
+  // the phases run one after the other by default; MS_OVERLAP=1 (S.overlap) turns the overlap on.
   struct Ctx {
     hipStream_t stream = nullptr;
     float* x = nullptr;
@@ -311,7 +182,6 @@ struct ms_engine {
     size_t args_cap = 0;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
   } cp, cd;
-  bool overlap = false;
   void use(const Ctx& c) {
     stream = c.stream; x = c.x; ssq = c.ssq; xb = c.xb; qkv = c.qkv; attn = c.attn; hbuf = c.hbuf;
     logits = c.logits; ids_out_d = c.ids_out_d; args_d = c.args_d; args_h = c.args_h;
@@ -335,16 +205,10 @@ struct ms_engine {
   std::map<std::tuple<int, int, int, int>, std::pair<hipGraphExec_t, uint64_t>> decode_graphs;
   uint64_t graph_clock = 0;
   static constexpr size_t kMaxGraphs = 64;
-  // chained decode steps per graph launch (MS_GRAPH_STEPS): 16 measured 12.12 -> 12.20
-  // chunks/s on configs[1], unchanged on the ragged level and configs[2]
-  // (profiles/r02/v35_graph_steps_ab.txt); a run's remainder uses the one-step graph
-  int graph_steps = 16;
-  bool use_graphs = true;
   int32_t* ids_host = nullptr;  // pinned landing buffer: kMaxRun steps x <= 256 greedy ids
   int32_t* first_host = nullptr;  // pinned: the first greedy id of each prefilled prompt
   int32_t* ids_ring_d = nullptr;  // device ring of a decode run's ids (decode_advance)
-  static constexpr int kMaxRun = 64;  // chained decode steps per host synchronisation
-  int max_run = kMaxRun;              // MS_DECODE_RUN (1 = one step per ms_step)
+  static constexpr int kMaxRun = 64;  // chained decode steps per host synchronisation (S.max_run)
   // Sampled decoding (k_sample.hip): every slot's sampler state lives on the device -- its
   // parameters, the repeat-penalty window ring and the per-request step counter -- written once
   // at admission (the window seeded from the prompt's tail) and advanced only by the kernels, so
@@ -429,25 +293,52 @@ struct ms_engine {
     prof_end(cls);
   }
 
-  // decode projection: the K-quant stream when that matrix was loaded quantised; above
-  // kMaxGemvRows rows (row groups) the rows go in groups, out elements of `esz` bytes
-  void proj(const QSlot* q, const f16_t* X, const f16_t* W, void* out, int M, int N, int K,
-            int ldo, int epi, const GemvArgs* ga, int cls, int esz = 0) {
-    if (row_groups(M)) {
+  DecodeMat mat(int which, int l) const {
+    if (which == QS_LM) return decode_mat(S, which, &lmq, lm_head);
+    const f16_t* W[4] = {layers[l].wqkv, layers[l].wo, layers[l].wgu, layers[l].wdown};
+    return decode_mat(S, which, &lq[l][which], W[which]);
+  }
+
+  // THE launch switch: one launcher per kernel family (pick_form ranks them).  The GEMV families
+  // take their deferred row scale in ga->rs, the GEMM families in rs; slabs: out = fp32 [S][M][N].
+  void launch_form(const Form& f, const DecodeMat& m, const f16_t* X, void* out, int M, int ldo, int epi,
+                   const GemvArgs* ga, const RowScale* rs, int cls) {
+    REQUIRE(f.family != F_NONE, MS_EIO, "no decode kernel takes this projection");
+    const int N = m.N, K = m.K;
+    prof_begin(cls);
+    switch (f.family) {
+      case F_GEMV:
+        if (f.slabs) launch_gemv_split(X, m.W, (float*)out, M, N, K, f.S, 0, stream, ga);
+        else launch_gemv_ex(X, m.W, out, M, N, K, ldo, epi, ga, 0, stream);
+        break;
+      case F_QGEMV:
+        if (f.slabs && f.S > 1) launch_qgemv_split(X, m.q->m, (float*)out, M, N, K, f.S, stream, ga);
+        else launch_qgemv(X, m.q->m, out, M, N, K, ldo, epi, ga, stream);
+        break;
+      case F_DGEMM: launch_dgemm(X, m.W, out, M, N, K, f.S, ldo, epi, stream, rs, m.kh, dgemm_wn(m, M)); break;
+      case F_QDGEMM: launch_qdgemm(X, m.q->m, out, M, N, K, f.S, ldo, epi, stream, rs); break;
+      case F_QDGEMM_F16: launch_qdgemm_f16(X, m.W, out, M, N, K, f.S, ldo, epi, stream, rs); break;
+      default: launch_gemm(X, m.W, out, M, N, K, ldo, epi, stream, rs);  // F_GEMM128
+    }
+    prof_end(cls);
+  }
+
+  // decode projection with one output; above kMaxGemvRows rows in the small regime (row groups)
+  // the rows go in groups, out elements of `esz` bytes (dgemm_gate: FormCall's)
+  void proj(const DecodeMat& m, const f16_t* X, void* out, int M, int ldo, int epi, const GemvArgs* ga, int cls,
+            int esz = 0, bool dgemm_gate = false) {
+    if (S.row_groups(M)) {
       for (int r0 = 0; r0 < M; r0 += kMaxGemvRows) {
         GemvArgs g = ga ? *ga : GemvArgs{};
         g.rs = rs_rows(g.rs, r0);
-        proj(q, X + (size_t)r0 * K, W, (char*)out + (size_t)r0 * ldo * esz, std::min(M - r0, (int)kMaxGemvRows),
-             N, K, ldo, epi, &g, cls, esz);
+        proj(m, X + (size_t)r0 * m.K, (char*)out + (size_t)r0 * ldo * esz, std::min(M - r0, kMaxGemvRows), ldo, epi,
+             &g, cls, esz, dgemm_gate);
       }
       return;
     }
-    prof_begin(cls);
-    if (q && q->ready() && qgemv_supported(M, N, K, epi))
-      launch_qgemv(X, q->m, out, M, N, K, ldo, epi, ga, stream);
-    else
-      launch_gemv_ex(X, W, out, M, N, K, ldo, epi, ga, 0, stream);
-    prof_end(cls);
+    FormCall c{M, epi};
+    c.dgemm_gate = dgemm_gate;
+    launch_form(pick_form(S, m, c), m, X, out, M, ldo, epi, ga, ga && ga->rs.ssq ? &ga->rs : nullptr, cls);
   }
 
   // decode with fused epilogues: QKV (split-K slabs, deferred norm scale) -> attention (folds
@@ -455,26 +346,26 @@ struct ms_engine {
   // into the residual and emit the next projection's input themselves (resid_fused) or write
   // split-K slabs that a residual_rmsnorm launch folds
   bool fused_decode(int B) const {
-    if (large(B))
-      return B <= kMaxSlabRows && attn_slabs && residual_rmsnorm_supported(kMaxSplit, H) &&
-             dgemm_supported(B, QKVN, H, dsplit_qkv, MS_GEMV_EPI_STORE_F32, 1) &&
-             dgemm_supported(B, H, Hq * D, dsplit_o, MS_GEMV_EPI_STORE_F32, 1) &&
-             dgemm_supported(B, H, F, dsplit_down, MS_GEMV_EPI_STORE_F32, 1) &&
-             dgemm_supported(B, 2 * F, H, 1, MS_GEMV_EPI_SWIGLU, dgemm_kh) && (2 * F) % 32 == 0 &&
+    if (S.large())
+      return B <= kMaxSlabRows && S.attn_slabs && residual_rmsnorm_supported(kMaxSplit, H) &&
+             dgemm_supported(B, QKVN, H, S.dsplit_qkv, MS_GEMV_EPI_STORE_F32, 1) &&
+             dgemm_supported(B, H, Hq * D, S.dsplit_o, MS_GEMV_EPI_STORE_F32, 1) &&
+             dgemm_supported(B, H, F, S.dsplit_down, MS_GEMV_EPI_STORE_F32, 1) &&
+             dgemm_supported(B, 2 * F, H, 1, MS_GEMV_EPI_SWIGLU, S.dgemm_kh) && (2 * F) % 32 == 0 &&
              attn_decode_supported(B, Hq, Hk, max_pages * kPage);
     // row groups (K-quant engines above 64 rows): split-K slabs and SwiGLU only, no residual
     // epilogue (resid_fused is off in large engines), one residual_rmsnorm over all rows
-    if (row_groups(B) && !(B <= kMaxSlabRows && attn_slabs && !resid_fused(nullptr))) return false;
-    const int Bg = std::min(B, (int)kMaxGemvRows);
+    if (S.row_groups(B) && !(B <= kMaxSlabRows && S.attn_slabs && !S.resid_fused(nullptr))) return false;
+    const int Bg = std::min(B, kMaxGemvRows);
     // the gate/up GEMV folds the statistics its producer wrote: 256 tiles behind the residual
     // epilogue, one behind residual_rmsnorm
-    const int gu_tiles = resid_fused(nullptr) ? H / resid_rt : 1;
+    const int gu_tiles = S.resid_fused(nullptr) ? H / S.resid_rt : 1;
     return residual_rmsnorm_supported(kMaxSplit, H) &&
-           (attn_slabs ? gemv_split_supported(Bg, QKVN, H, 1) : gemv_supported(Bg, QKVN, H, MS_GEMV_EPI_ROPE_KV)) &&
+           (S.attn_slabs ? gemv_split_supported(Bg, QKVN, H, 1) : gemv_supported(Bg, QKVN, H, MS_GEMV_EPI_ROPE_KV)) &&
            gemv_supported(Bg, 2 * F, H, MS_GEMV_EPI_SWIGLU, gu_tiles) &&
            gemv_split_supported(Bg, H, Hq * D, 1) && gemv_split_supported(Bg, H, F, 1) &&
-           (!resid_fuse || (gemv_supported(Bg, H, Hq * D, MS_GEMV_EPI_RESID_SSQ) &&
-                            gemv_supported(Bg, H, F, MS_GEMV_EPI_RESID_SSQ))) &&
+           (!S.resid_fuse || (gemv_supported(Bg, H, Hq * D, MS_GEMV_EPI_RESID_SSQ) &&
+                              gemv_supported(Bg, H, F, MS_GEMV_EPI_RESID_SSQ))) &&
            attn_decode_supported(B, Hq, Hk, max_pages * kPage);
   }
   // a row group's deferred-norm scale: one-tile statistics are per row ([M]), so the group
@@ -484,60 +375,24 @@ struct ms_engine {
     if (g.ssq) g.ssq += r0;
     return g;
   }
-  static constexpr int kMaxGemvRows = 64, kMaxSlabRows = 256, kMaxSplit = 8;
 
-  // normalised projection into fp32 partial slabs [S][M][N], rows scaled by cur_rs; returns
-  // the number of slabs written
-  // dwn: the skinny GEMM's weight-row groups per block (k_dgemm.hip wn; 8 = 128-row blocks,
-  // the same bits as 4) for launches of <= 128 rows
-  int proj_split(const QSlot* q, const f16_t* X, const f16_t* W, int M, int N, int K, int S, int Sl,
-                 const RowScale* rs, int dwn = 4) {
-    if (row_groups(M)) {
-      // every group must write the same number of slabs: the fold adds S slabs for all rows
-      int used = 0;
-      for (int r0 = 0; r0 < M; r0 += kMaxGemvRows) {
-        const RowScale g = rs ? rs_rows(*rs, r0) : RowScale{};
-        const int u = proj_split_rows(q, X + (size_t)r0 * K, W, std::min(M - r0, (int)kMaxGemvRows), N, K, S, Sl,
-                                      rs ? &g : nullptr, slabs + (size_t)r0 * N, M, dwn);
-        REQUIRE(used == 0 || u == used, MS_EIO, "row groups split a projection differently");
-        used = u;
-      }
-      return used;
+  // projection of xb's / attn's / hbuf's rows into unscaled fp32 partial slabs [S][M][N] (row
+  // groups write theirs into the batch's slabs); returns the number of slabs written
+  int proj_split(const DecodeMat& m, const f16_t* X, int M) {
+    // every group must write the same number of slabs: the fold adds S slabs for all rows
+    int used = 0;
+    const int step = S.row_groups(M) ? kMaxGemvRows : M;
+    for (int r0 = 0; r0 < M; r0 += step) {
+      const int rows = std::min(M - r0, step);
+      GemvArgs ga{};
+      ga.slab_rows = step < M ? M : 0;
+      FormCall c{rows, MS_GEMV_EPI_STORE_F32};
+      c.slabs = true;
+      const Form f = pick_form(S, m, c);
+      launch_form(f, m, X + (size_t)r0 * m.K, slabs + (size_t)r0 * m.N, rows, m.N, c.epi, &ga, nullptr, K_GEMV);
+      REQUIRE(used == 0 || f.S == used, MS_EIO, "row groups split a projection differently");
+      used = f.S;
     }
-    return proj_split_rows(q, X, W, M, N, K, S, Sl, rs, slabs, 0, dwn);
-  }
-  int proj_split_rows(const QSlot* q, const f16_t* X, const f16_t* W, int M, int N, int K, int S, int Sl,
-                      const RowScale* rs, float* slabs, int slab_rows, int dwn) {
-    prof_begin(K_GEMV);
-    GemvArgs ga{};
-    if (rs) ga.rs = *rs;
-    ga.slab_rows = slab_rows;
-    int used = 1;
-    if (large(M)) {  // skinny GEMM: the packed K-quant blocks, or the fp16 weights
-      if (qd(q, M, N, K, Sl, MS_GEMV_EPI_STORE_F32))
-        launch_qdgemm(X, q->m, slabs, M, N, K, Sl, N, MS_GEMV_EPI_STORE_F32, stream, rs);
-      else if (qdf(M, N, K, Sl, MS_GEMV_EPI_STORE_F32))
-        launch_qdgemm_f16(X, W, slabs, M, N, K, Sl, N, MS_GEMV_EPI_STORE_F32, stream, rs);
-      else
-        launch_dgemm(X, W, slabs, M, N, K, Sl, N, MS_GEMV_EPI_STORE_F32, stream, rs, 1,
-                     M <= 128 && N % 128 == 0 ? dwn : 4);
-      used = Sl;
-    } else if (q && q->ready() && qgemv_supported(M, N, K, MS_GEMV_EPI_STORE_F32)) {
-      // Q4_K/Q6_K: same split-K as fp16 (a 16-row tile carries 3.6x fewer weight bytes, so
-      // the unsplit grid -- 192 blocks for O/down -- is too thin to cover 256 CUs)
-      const int Sq = qsplit > 0 ? qsplit : S;
-      if (Sq > 1 && Sq <= kMaxSplit && qgemv_split_supported(M, N, K, Sq)) {
-        launch_qgemv_split(X, q->m, slabs, M, N, K, Sq, stream, &ga);
-        used = Sq;
-      } else {
-        launch_qgemv(X, q->m, slabs, M, N, K, N, MS_GEMV_EPI_STORE_F32, &ga, stream);
-      }
-    } else {
-      if (!(S >= 1 && S <= kMaxSplit && gemv_split_supported(M, N, K, S))) S = 1;
-      launch_gemv_split(X, W, slabs, M, N, K, S, 0, stream, &ga);
-      used = S;
-    }
-    prof_end(K_GEMV);
     return used;
   }
 
@@ -553,75 +408,49 @@ struct ms_engine {
   // the residual update of O / down: x += X . W^T, then the input of the next normalised
   // projection (gain g_next) -- in the GEMV epilogue (resid_fused: RESID_SSQ on resid_rt-row
   // tiles, 256 tiles of statistics) or as split-K slabs + one residual_rmsnorm launch
-  void resid_update(const QSlot* q, const f16_t* X, const f16_t* W, int B, int K, int S, int Sl,
-                    const f16_t* g_next, int dwn) {
-    if (resid_fused(q)) {
+  void resid_update(const DecodeMat& m, const f16_t* X, int B, const f16_t* g_next) {
+    if (S.resid_fused(m.q)) {
       GemvArgs ga{};
-      ga.rt = resid_rt;
+      ga.rt = S.resid_rt;
       ga.ssq_out = ssq;
       ga.gamma = g_next;
       ga.xg_out = xb;
-      prof_begin(K_GEMV);
-      if (q && q->ready())
-        launch_qgemv(X, q->m, x, B, H, K, H, MS_GEMV_EPI_RESID_SSQ, &ga, stream);
-      else
-        launch_gemv_ex(X, W, x, B, H, K, H, MS_GEMV_EPI_RESID_SSQ, &ga, 0, stream);
-      prof_end(K_GEMV);
+      FormCall c{B, MS_GEMV_EPI_RESID_SSQ};
+      c.presupported = true;
+      launch_form(pick_form(S, m, c), m, X, x, B, H, c.epi, &ga, nullptr, K_GEMV);
       pending_split = 0;
-      cur_rs = make_row_scale(ssq, H / resid_rt, H, cfg.norm_eps);
+      cur_rs = make_row_scale(ssq, H / S.resid_rt, H, cfg.norm_eps);
     } else {
-      pending_split = proj_split(q, X, W, B, H, K, S, Sl, nullptr, dwn);
+      pending_split = proj_split(m, X, B);
       residual_norm(g_next, B);
     }
   }
 
   void run_layer_fused_decode(int l, int B, const int32_t* tok_pos, const int32_t* tok_slot,
                               const DecodeAttnArgs& da) {
-    const Layer& Ly = layers[l];
     KVView kv = kv_layer(l);
-    const auto& Q = lq[l];
     const RowScale rs_attn = cur_rs;
     DecodeQKV qa{nullptr, slabs, 0, cos_tab, sin_tab, rs_attn};
-    if (attn_slabs) {
+    if (S.attn_slabs) {
       // QKV -> unscaled slabs; attention adds them, applies the row's deferred-norm factor and
       // RoPE, and writes the new K/V (k_attn.hip): one factor per attention block, not per
       // QKV tile
-      qa.S = proj_split(&Q[QS_QKV], xb, Ly.wqkv, B, QKVN, H, split_qkv, dsplit_qkv, nullptr, dwn_qkv);
+      qa.S = proj_split(mat(QS_QKV, l), xb, B);
     } else {
       // QKV GEMV epilogue: RoPE, q -> qkv rows, K/V -> paged cache
-      GemvArgs ga{};
-      ga.tok_pos = tok_pos;
-      ga.tok_slot = tok_slot;
-      ga.cos_tab = cos_tab;
-      ga.sin_tab = sin_tab;
-      ga.kv = kv;
-      ga.Hq = Hq;
-      ga.Hk = Hk;
+      GemvArgs ga{tok_pos, tok_slot, cos_tab, sin_tab, kv, Hq, Hk};
       ga.rs = rs_attn;
-      proj(&Q[QS_QKV], xb, Ly.wqkv, qkv, B, QKVN, H, QKVN, MS_GEMV_EPI_ROPE_KV, &ga, K_GEMV);
+      proj(mat(QS_QKV, l), xb, qkv, B, QKVN, MS_GEMV_EPI_ROPE_KV, &ga, K_GEMV);
       qa = DecodeQKV{qkv, nullptr, 0, cos_tab, sin_tab, RowScale{}};
     }
     attn_decode(qa, kv, da);
-    resid_update(&Q[QS_O], attn, Ly.wo, B, Hq * D, split_o, dsplit_o, Ly.ffn_norm, dwn_o);
-    const RowScale rs_ffn = cur_rs;
-    const f16_t* g_next = l + 1 < L ? layers[l + 1].attn_norm : final_norm;
-    if (large(B)) {
-      // gate/up + SwiGLU on the skinny GEMM (41 vs 55 us for the 128x128 GEMM at M = 128,
-      // profiles/r02/v7_dgemm_lds_sync_ab.txt; fused_decode checked M <= 256)
-      prof_begin(K_GEMV);
-      if (qd(&Q[QS_GU], B, 2 * F, H, 1, MS_GEMV_EPI_SWIGLU))
-        launch_qdgemm(xb, Q[QS_GU].m, hbuf, B, 2 * F, H, 1, F, MS_GEMV_EPI_SWIGLU, stream, &rs_ffn);
-      else if (qdf(B, 2 * F, H, 1, MS_GEMV_EPI_SWIGLU))
-        launch_qdgemm_f16(xb, Ly.wgu, hbuf, B, 2 * F, H, 1, F, MS_GEMV_EPI_SWIGLU, stream, &rs_ffn);
-      else
-        launch_dgemm(xb, Ly.wgu, hbuf, B, 2 * F, H, 1, F, MS_GEMV_EPI_SWIGLU, stream, &rs_ffn, dgemm_kh);
-      prof_end(K_GEMV);
-    } else {
-      GemvArgs gg{};
-      gg.rs = rs_ffn;
-      proj(&Q[QS_GU], xb, Ly.wgu, hbuf, B, 2 * F, H, F, MS_GEMV_EPI_SWIGLU, &gg, K_GEMV, sizeof(f16_t));
-    }
-    resid_update(&Q[QS_DOWN], hbuf, Ly.wdown, B, F, split_down, dsplit_down, g_next, dwn_down);
+    resid_update(mat(QS_O, l), attn, B, layers[l].ffn_norm);
+    // gate/up + SwiGLU; in the large regime on a skinny GEMM (41 vs 55 us for the 128x128 GEMM at
+    // M = 128, profiles/r02/v7_dgemm_lds_sync_ab.txt; fused_decode checked M <= 256)
+    GemvArgs gg{};
+    gg.rs = cur_rs;
+    proj(mat(QS_GU, l), xb, hbuf, B, F, MS_GEMV_EPI_SWIGLU, &gg, K_GEMV, sizeof(f16_t));
+    resid_update(mat(QS_DOWN, l), hbuf, B, l + 1 < L ? layers[l + 1].attn_norm : final_norm);
   }
 
   // one transformer layer over T packed tokens (decode: T = B rows, one token each); on entry
@@ -771,25 +600,6 @@ struct ms_engine {
 
 namespace {
 
-int fail(ms_engine* e, const MsError& x) {
-  if (e) e->err = x.what();
-  g_last_error = x.what();
-  return x.code;
-}
-
-template <class Fn>
-int guarded(ms_engine* e, Fn&& fn) {
-  try {
-    return fn();
-  } catch (const MsError& x) {
-    return fail(e, x);
-  } catch (const std::exception& x) {
-    return fail(e, MsError(MS_EIO, x.what()));
-  } catch (...) {
-    return fail(e, MsError(MS_EIO, "unknown exception"));
-  }
-}
-
 // llama3-scaled rotate-half tables (oracle/llama_ref.py rope_inv_freq restates this)
 void rope_tables(const ms_config& c, int max_ctx, std::vector<float>& cs, std::vector<float>& sn) {
   const int half = c.head_dim / 2;
@@ -848,10 +658,11 @@ int ms_create(const ms_config* cfg, ms_engine** out) {
   }
   *out = nullptr;
   auto e = std::make_unique<ms_engine>();
-  int rc = guarded(nullptr, [&]() -> int {
+  int rc = guarded((ms_engine*)nullptr, [&]() -> int {
     validate_config(*cfg);
     ms_engine& E = *e;
     E.cfg = *cfg;
+    E.S = resolve_settings(*cfg);
     HIP_OK(hipSetDevice(cfg->device));
     for (ms_engine::Ctx* c : {&E.cp, &E.cd}) {
       HIP_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -864,7 +675,7 @@ int ms_create(const ms_config* cfg, ms_engine** out) {
     E.QKVN = (E.Hq + 2 * E.Hk) * E.D;
     E.max_pages = (cfg->max_ctx + kPage - 1) / kPage;
     E.n_pages = cfg->n_pages > 0 ? cfg->n_pages : cfg->max_batch * E.max_pages;
-    E.slot_major = E.n_pages == cfg->max_batch * E.max_pages && !getenv("MS_KV_PAGED");
+    E.slot_major = E.n_pages == cfg->max_batch * E.max_pages && !E.S.kv_paged;
     E.Tmax = std::max(cfg->max_prefill_tokens, cfg->max_batch);
     // weights
     E.embed = E.dalloc<f16_t>((size_t)E.V * E.H);
@@ -916,11 +727,6 @@ int ms_create(const ms_config* cfg, ms_engine** out) {
     const int shapes[5][2] = {{E.QKVN, E.H}, {E.H, E.Hq * E.D}, {2 * E.F, E.H}, {E.H, E.F}, {E.V, E.H}};
     for (auto& sh : shapes) gws = std::max(gws, gemv_workspace_bytes(Md, sh[0], sh[1]));
     E.gemv_ws = E.dalloc<char>(gws, true);
-    // decode attention: v2 (one page per wave) for engines of <= 16 slots (MS_ATTN_V2 overrides)
-    E.attn_ppb = attn_decode2_ppb(cfg->max_batch, E.Hk, cfg->max_ctx);
-    E.attn_v2 = cfg->max_batch <= 16;
-    if (const char* v = getenv("MS_ATTN_V2")) E.attn_v2 = atoi(v) != 0;
-    if (const char* v = getenv("MS_ATTN_TICKET")) E.attn_ticket = atoi(v) != 0;
     E.attn_cnt = E.dalloc<unsigned>((size_t)cfg->max_batch * E.Hk, true);
     // decode_run sets the split grid from the longest sequence rounded UP to 256 keys, which can
     // pass max_ctx when max_ctx is not a multiple of 256: size both attention
@@ -928,55 +734,15 @@ int ms_create(const ms_config* cfg, ms_engine** out) {
     const int ws_ctx = (cfg->max_ctx + 255) / 256 * 256;
     E.attn_ws = (float*)E.dalloc<char>(std::max(attn_decode_workspace_bytes(cfg->max_batch, E.Hq, ws_ctx),
                                                 attn_decode2_workspace_bytes(cfg->max_batch, E.Hq, ws_ctx,
-                                                                             E.attn_ppb)),
+                                                                             E.S.attn_ppb)),
                                        true);
-    E.slabs = E.dalloc<float>((size_t)ms_engine::kMaxSplit * std::min(std::max(cfg->max_batch, 64), 256) *
+    E.slabs = E.dalloc<float>((size_t)kMaxSplit * std::min(std::max(cfg->max_batch, 64), 256) *
                               std::max(E.QKVN, E.H));
-    if (const char* v = getenv("MS_SPLIT_QKV")) E.split_qkv = atoi(v);
-    if (const char* v = getenv("MS_ATTN_SLABS")) E.attn_slabs = atoi(v) != 0;
-    if (const char* v = getenv("MS_SPLIT_O")) E.split_o = atoi(v);
-    if (const char* v = getenv("MS_SPLIT_DOWN")) E.split_down = atoi(v);
-    if (const char* v = getenv("MS_DGEMM_MIN")) E.dgemm_min = atoi(v);
-    E.large_engine = cfg->max_batch >= E.dgemm_min;
-    if (const char* v = getenv("MS_QLARGE_MIN")) E.qlarge_min = atoi(v);
-    if (const char* v = getenv("MS_QDGEMM")) E.qdgemm_mode = atoi(v);
-    if (const char* v = getenv("MS_LM_GEMM_MIN")) E.lm_gemm_min = atoi(v);
-    // (the k-half block steps 128 k at a time: hidden sizes that are not a multiple of 128
-    // keep the 4-wave block)
-    E.dgemm_kh = cfg->max_batch <= 128 && E.H % 128 == 0 ? dgemm_kh_setting() : 1;
-    if (const char* v = getenv("MS_QDF_MIN")) E.qdf_min = atoi(v);
-    if (E.qdf_min > 0 && cfg->max_batch >= E.qdf_min) {  // splits measured at 256 rows (v22_*), any weights
-      E.dsplit_qkv = 3;
-      E.dsplit_down = 4;
-    }
-    if (const char* v = getenv("MS_DSPLIT_QKV")) E.dsplit_qkv = atoi(v);
-    if (const char* v = getenv("MS_DSPLIT_O")) E.dsplit_o = atoi(v);
-    if (const char* v = getenv("MS_DSPLIT_DOWN")) E.dsplit_down = atoi(v);
-    if (const char* v = getenv("MS_DWN")) E.dwn_qkv = E.dwn_o = E.dwn_down = E.dwn_lm = atoi(v) == 8 ? 8 : 4;
-    for (int* d : {&E.dsplit_qkv, &E.dsplit_o, &E.dsplit_down}) *d = std::min(std::max(*d, 1), (int)ms_engine::kMaxSplit);
-    E.attn_ppw = attn_decode_ppw(cfg->max_batch, E.Hk, cfg->max_ctx);
-    if (const char* v = getenv("MS_QSPLIT")) E.qsplit = atoi(v);
-    if (const char* v = getenv("MS_RESID_FUSED")) E.resid_fuse = atoi(v) != 0;
-    if (const char* v = getenv("MS_DECODE_TAIL")) E.tail_fuse = atoi(v) != 0;
-    if (const char* v = getenv("MS_QRESID")) E.qresid = atoi(v) != 0;
-    if (E.H % E.resid_rt || E.H / E.resid_rt > 256) E.resid_rt = 16;
-    if (E.H % E.resid_rt || E.H / E.resid_rt > 256) E.resid_fuse = false;
-    // the consumers stage the 256-tile statistics in LDS: engines of <= 16 slots (per engine,
-    // so every step of it runs the same arithmetic)
-    if (!gemv_rs_supported(cfg->max_batch, E.H / E.resid_rt)) E.resid_fuse = false;
-    {
-      const int Bg = std::min(cfg->max_batch, (int)ms_engine::kMaxGemvRows);
-      E.qresid_ok = qgemv_supported(Bg, E.H, E.Hq * E.D, MS_GEMV_EPI_RESID_SSQ) &&
-                    qgemv_supported(Bg, E.H, E.F, MS_GEMV_EPI_RESID_SSQ) &&
-                    qgemv_supported(Bg, 2 * E.F, E.H, MS_GEMV_EPI_SWIGLU, E.H / E.resid_rt);
-    }
-    if (const char* v = getenv("MS_GRAPH_STEPS")) E.graph_steps = std::max(1, std::min(atoi(v), 16));
     for (ms_engine::Ctx* c : {&E.cp, &E.cd}) {
       c->args_cap = 8 * T + 64 * (size_t)cfg->max_batch + (size_t)cfg->max_batch * E.max_pages + 1024;
       c->args_d = E.dalloc<int32_t>(c->args_cap);
       HIP_OK(hipHostMalloc((void**)&c->args_h, c->args_cap * sizeof(int32_t), hipHostMallocDefault));
     }
-    if (const char* v = getenv("MS_OVERLAP")) E.overlap = atoi(v) != 0;
     E.use(E.cp);
     HIP_OK(hipHostMalloc((void**)&E.ids_host, (size_t)ms_engine::kMaxRun * 256 * sizeof(int32_t),
                          hipHostMallocDefault));
@@ -986,11 +752,10 @@ int ms_create(const ms_config* cfg, ms_engine** out) {
       int dev_cu = 0;
       HIP_OK(hipDeviceGetAttribute(&dev_cu, hipDeviceAttributeMultiprocessorCount, cfg->device));
       E.n_cu = dev_cu;
-      if (const char* v = getenv("MS_PERSIST")) E.persist = atoi(v) != 0;
       const int np_ws = (ws_ctx + kPage - 1) / kPage;
-      E.nsplit_ws = (np_ws + E.attn_ppb - 1) / E.attn_ppb;
-      E.persist_ok = persist_supported(cfg->max_batch, E.H, E.F, E.Hq, E.Hk, E.D, E.L, E.attn_ppb, E.n_cu) &&
-                     E.slot_major && E.attn_v2 && E.resid_rt == 12;
+      E.nsplit_ws = (np_ws + E.S.attn_ppb - 1) / E.S.attn_ppb;
+      E.persist_ok = persist_supported(cfg->max_batch, E.H, E.F, E.Hq, E.Hk, E.D, E.L, E.S.attn_ppb, E.n_cu) &&
+                     E.slot_major && E.S.attn_v2 && E.S.resid_rt == 12;
       E.pk_sync = E.dalloc<unsigned>(persist_sync_words(E.L), true);
       E.pk_err_d = E.dalloc<unsigned>(4, true);
       HIP_OK(hipHostMalloc((void**)&E.pk_err_h, 64, hipHostMallocDefault));
@@ -1002,8 +767,6 @@ int ms_create(const ms_config* cfg, ms_engine** out) {
     E.samp_d = E.dalloc<SampleSlot>(cfg->max_batch, true);
     HIP_OK(hipHostMalloc((void**)&E.samp_h, (size_t)cfg->max_batch * sizeof(SampleSlot), hipHostMallocDefault));
     E.slot_sampled.assign(cfg->max_batch, 0);
-    if (const char* v = getenv("MS_DECODE_RUN")) E.max_run = std::max(1, std::min(atoi(v), (int)ms_engine::kMaxRun));
-    if (const char* ng = getenv("MAPSUM_NO_GRAPHS")) E.use_graphs = !(ng[0] == '1');
     HIP_OK(hipDeviceSynchronize());
     return MS_OK;
   });
@@ -1154,7 +917,7 @@ static void load_quant(ms_engine& E, int tensor, int layer, int type, const uint
   uint8_t* q = t.qs ? q_region(E, *t.qs, t.qregion, t.qrow0, t.qrows, type, t.cols) : nullptr;
   launch_quant_rows(type, dblocks, t.rows, t.cols, t.dst, t.mul, t.add, q, t.qrow0, E.stream);
   HIP_OK(hipGetLastError());
-  E.has_quant = true;  // the K-quant decode GEMVs have no norm prologue: the unfused step
+  E.S.has_quant = true;  // the K-quant decode GEMVs have no norm prologue: the unfused step
   if (t.qs) {
     t.qs->loaded |= (uint32_t)t.qbit;
     t.qs->need = (uint32_t)t.qneed;
@@ -1201,7 +964,7 @@ int ms_declare_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t typ
     TensorDst t = tensor_dst(E, tensor, layer);
     REQUIRE(t.rows > 1 && t.cols % 256 == 0, MS_EINVAL, "not a quantisable matrix");
     E.check_quant_family(type);
-    E.has_quant = true;
+    E.S.has_quant = true;
     if (t.qs) {  // the layout of a quantised load, without its bytes (a broadcast fills them)
       q_region(E, *t.qs, t.qregion, t.qrow0, t.qrows, type, t.cols);
       t.qs->loaded |= (uint32_t)t.qbit;
@@ -1566,8 +1329,8 @@ static void prefill(ms_engine& E, std::vector<Seq*>& batch, int n_layers_run, fl
   E.norm_input(E.final_norm, S, d + o_last);
   // the first token goes through the decode lm_head GEMV in row groups of <= 64: its sum
   // order is then the decode steps' one whatever the number of admitted prompts
-  for (int r0 = 0; r0 < S; r0 += ms_engine::kMaxGemvRows) {
-    const int rows = std::min(S - r0, (int)ms_engine::kMaxGemvRows);
+  for (int r0 = 0; r0 < S; r0 += kMaxGemvRows) {
+    const int rows = std::min(S - r0, kMaxGemvRows);
     const RowScale rs = make_row_scale(E.ssq + r0, 1, E.H, E.cfg.norm_eps);
     E.gemm_or_gemv(E.xb + (size_t)r0 * E.H, E.lm_head, E.logits + (size_t)r0 * E.V, rows, E.V, E.H, E.V,
                    MS_EPI_STORE_F32, true, K_LMHEAD, &rs);
@@ -1576,10 +1339,7 @@ static void prefill(ms_engine& E, std::vector<Seq*>& batch, int n_layers_run, fl
   for (Seq* s : batch) samp = samp || s->sampled;
   E.prof_begin(K_MISC);
   if (samp) {  // step 0 of the sampling chunks (greedy rows: the same argmax), state advanced
-    SampleArgs sa{};
-    sa.logits = E.logits;
-    sa.ldl = E.V;
-    sa.n = E.V;
+    SampleArgs sa{E.logits, E.V, E.V};
     sa.slots = E.samp_d;
     sa.row_slot = d + o_sslot;
     sa.ids_out = E.ids_out_d;
@@ -1608,7 +1368,7 @@ static void decode_head(ms_engine& E, int B, int32_t* d) {
 // (MS_DECODE_TAIL=0: the three launches; the same bits either way)
 static void decode_tail(ms_engine& E, int B, int32_t* d, int tiles) {
   E.prof_begin(K_MISC);
-  if (E.tail_fuse && B <= 256) {
+  if (E.S.tail_fuse && B <= 256) {
     launch_decode_tail(E.logits, tiles, d, E.ids_out_d, E.ids_ring_d, B, E.V, E.embed, E.H, E.x,
                        E.layers[0].attn_norm, E.xb, E.ssq, E.stream);
     E.prof_end(K_MISC);
@@ -1637,7 +1397,7 @@ static void persist_layers(ms_engine& E, int B, const DecodeAttnArgs& da) {
   a.seq_len = da.seq_len;
   a.seq_slot = da.seq_slot;
   a.max_pages = E.max_pages;
-  a.ppb = E.attn_ppb;
+  a.ppb = E.S.attn_ppb;
   a.nsplit_ws = E.nsplit_ws;
   a.cos_tab = E.cos_tab;
   a.sin_tab = E.sin_tab;
@@ -1660,52 +1420,39 @@ static void persist_layers(ms_engine& E, int B, const DecodeAttnArgs& da) {
   launch_decode_step(a, E.stream);
   E.prof_end(K_PERSIST);
   E.pending_split = 0;
-  E.cur_rs = make_row_scale(E.ssq, E.H / E.resid_rt, E.H, E.cfg.norm_eps);
+  E.cur_rs = make_row_scale(E.ssq, E.H / E.S.resid_rt, E.H, E.cfg.norm_eps);
+}
+
+// The lm_head of a decode step in the regime's own kernel family and weight form (pick_form).
+// Greedy: {max, id} partials per 16-column tile [B][V / 16] -- no logits row and no row scale
+// (r > 0 keeps every row's order).  Sampling: fp32 logits [B][V] with the deferred row scale.
+// False when no family takes the shape: the caller falls to gemm_or_gemv.
+static bool lm_head(ms_engine& E, int B, bool samp) {
+  DecodeMat lm = E.mat(QS_LM, 0);
+  const RowScale rs = E.cur_rs;
+  FormCall c{B, samp ? MS_GEMV_EPI_STORE_F32 : MS_GEMV_EPI_ARGMAX, samp ? rs.tiles : 0};
+  c.lm_gate = true;
+  c.dgemm_gate = !samp;
+  const Form f = pick_form(E.S, lm, c);
+  if (f.family == F_NONE) return false;
+  const int ldo = samp ? E.V : E.V / 16;
+  if (!small_family(f.family)) {
+    E.launch_form(f, lm, E.xb, E.logits, B, ldo, c.epi, nullptr, samp ? &rs : nullptr, K_LMHEAD);
+    return true;
+  }
+  // row groups are ranked again; sampling keeps the Q-GEMV only where it stages the statistics at full group size
+  if (samp && f.family != F_QGEMV) lm.q = nullptr;
+  GemvArgs ga{};
+  ga.rs = rs;
+  E.proj(lm, E.xb, E.logits, B, ldo, c.epi, samp ? &ga : nullptr, K_LMHEAD, samp ? sizeof(float) : sizeof(float2),
+         c.dgemm_gate);
+  return true;
 }
 
 // kernels of one decode step (no host synchronisation: capturable into a hipGraph).  Enters
-// with the step's layer-0 input in x / xb / ssq and leaves the NEXT step's there: the greedy
-// ids, the argument advance and the next embedding gather are one launch (decode_tail_kernel)
-// on the argmax-partials lm_head paths.
-// A sampling run's lm_head and tail: the regime's own kernel family and weight form with the
-// fp32 store epilogue and the deferred row scale into E.logits [B][V], then the fused sampling
-// tail.  GEMV / Q-GEMV row groups, the skinny GEMM, the K-quant skinny GEMM and the 128x128 tile
-// all have that epilogue; a shape none of them takes falls to gemm_or_gemv like the greedy body.
-static void decode_sampled_tail(ms_engine& E, int B, int32_t* d) {
-  const RowScale rs = E.cur_rs;
-  const int Bg = std::min(B, (int)ms_engine::kMaxGemvRows);
-  bool done = false;
-  if (E.large(B)) {
-    E.prof_begin(K_LMHEAD);
-    if (rs.tiles == 1 && E.qd(&E.lmq, B, E.V, E.H, 1, MS_GEMV_EPI_STORE_F32)) {
-      launch_qdgemm(E.xb, E.lmq.m, E.logits, B, E.V, E.H, 1, E.V, MS_GEMV_EPI_STORE_F32, E.stream, &rs);
-      done = true;
-    } else if (E.lm_gemm_min > 0 && E.cfg.max_batch >= E.lm_gemm_min && E.H % 64 == 0 &&
-               gemm_rs_tiles_ok(B, E.V, rs.tiles)) {
-      launch_gemm(E.xb, E.lm_head, E.logits, B, E.V, E.H, E.V, MS_EPI_STORE_F32, E.stream, &rs);
-      done = true;
-    } else if (rs.tiles == 1 && dgemm_supported(B, E.V, E.H, 1, MS_GEMV_EPI_STORE_F32, 1,
-                                                B <= 128 && E.V % 128 == 0 ? E.dwn_lm : 4)) {
-      launch_dgemm(E.xb, E.lm_head, E.logits, B, E.V, E.H, 1, E.V, MS_GEMV_EPI_STORE_F32, E.stream, &rs, 1,
-                   B <= 128 && E.V % 128 == 0 ? E.dwn_lm : 4);
-      done = true;
-    }
-    E.prof_end(K_LMHEAD);
-  } else if (gemv_supported(Bg, E.V, E.H, MS_GEMV_EPI_STORE_F32, rs.tiles) &&
-             (B <= ms_engine::kMaxGemvRows || (E.row_groups(B) && rs.tiles == 1))) {
-    GemvArgs ga{};
-    ga.rs = rs;
-    const QSlot* q = E.lmq.ready() && qgemv_supported(Bg, E.V, E.H, MS_GEMV_EPI_STORE_F32, rs.tiles) ? &E.lmq : nullptr;
-    E.proj(q, E.xb, E.lm_head, E.logits, B, E.V, E.H, E.V, MS_GEMV_EPI_STORE_F32, &ga, K_LMHEAD, sizeof(float));
-    done = true;
-  }
-  if (!done) E.gemm_or_gemv(E.xb, E.lm_head, E.logits, B, E.V, E.H, E.V, MS_EPI_STORE_F32, true, K_LMHEAD, &rs);
-  E.prof_begin(K_MISC);
-  launch_sample_tail(E.logits, E.samp_d, d, E.ids_out_d, E.ids_ring_d, B, E.V, E.embed, E.H, E.x,
-                     E.layers[0].attn_norm, E.xb, E.ssq, E.stream);
-  E.prof_end(K_MISC);
-}
-
+// with the step's layer-0 input in x / xb / ssq and leaves the NEXT step's there: the ids, the
+// argument advance and the next embedding gather are one launch on the argmax-partials lm_head
+// paths (decode_tail_kernel) and behind a sampling run's stored logits (the fused sampling tail).
 static void decode_body(ms_engine& E, int B, int32_t* d, const DecodeAttnArgs& da, bool samp = false) {
   const size_t o_pos = B, o_slot = 2 * (size_t)B;
   PrefillAttnArgs pa{};
@@ -1717,39 +1464,23 @@ static void decode_body(ms_engine& E, int B, int32_t* d, const DecodeAttnArgs& d
     // every layer leaves xb = f16(x * the next gain) with its deferred scale in cur_rs
     for (int l = 0; l < E.L; ++l) E.run_layer(l, B, true, d + o_pos, d + o_slot, pa, da);
   }
-  if (samp) {
-    decode_sampled_tail(E, B, d);
+  const bool fused = lm_head(E, B, samp);
+  if (!fused) {
+    const RowScale rs = E.cur_rs;
+    E.gemm_or_gemv(E.xb, E.lm_head, E.logits, B, E.V, E.H, E.V, MS_EPI_STORE_F32, true, K_LMHEAD, &rs);
+  }
+  if (fused && !samp) {
+    decode_tail(E, B, d, E.V / 16);
     return;
   }
-  const RowScale rs = E.cur_rs;
-  if (E.large(B) && dgemm_supported(B, E.V, E.H, 1, MS_GEMV_EPI_ARGMAX, 1)) {
-    const int tiles = E.V / 16;
-    E.prof_begin(K_LMHEAD);
-    // no row scale: r > 0 keeps every row's order (the logits themselves are never stored)
-    // 4-wave blocks always: a 2004-block grid keeps two per CU (k_dgemm.hip kh)
-    if (E.qd(&E.lmq, B, E.V, E.H, 1, MS_GEMV_EPI_ARGMAX))
-      launch_qdgemm(E.xb, E.lmq.m, E.logits, B, E.V, E.H, 1, tiles, MS_GEMV_EPI_ARGMAX, E.stream, nullptr);
-    else if (E.lm_gemm_min > 0 && E.cfg.max_batch >= E.lm_gemm_min && E.H % 64 == 0 && E.V % 16 == 0)
-      launch_gemm(E.xb, E.lm_head, E.logits, B, E.V, E.H, tiles, MS_GEMV_EPI_ARGMAX, E.stream);
-    else
-      launch_dgemm(E.xb, E.lm_head, E.logits, B, E.V, E.H, 1, tiles, MS_GEMV_EPI_ARGMAX, E.stream, nullptr, 1,
-                   B <= 128 && E.V % 128 == 0 ? E.dwn_lm : 4);
-    E.prof_end(K_LMHEAD);
-    decode_tail(E, B, d, tiles);
-    return;
-  } else if (gemv_supported(std::min(B, (int)ms_engine::kMaxGemvRows), E.V, E.H, MS_GEMV_EPI_ARGMAX) &&
-             (B <= ms_engine::kMaxGemvRows || E.row_groups(B))) {
-    // greedy argmax in the lm_head epilogue: {max, id} per 16-column tile, no logits row
-    const int tiles = E.V / 16;
-    E.proj(&E.lmq, E.xb, E.lm_head, E.logits, B, E.V, E.H, tiles, MS_GEMV_EPI_ARGMAX, nullptr, K_LMHEAD,
-           sizeof(float2));
-    decode_tail(E, B, d, tiles);
-    return;
-  }
-  E.gemm_or_gemv(E.xb, E.lm_head, E.logits, B, E.V, E.H, E.V, MS_EPI_STORE_F32, true, K_LMHEAD, &rs);
   E.prof_begin(K_MISC);
-  launch_argmax(E.logits, B, E.V, E.ids_out_d, E.stream);
+  if (samp)
+    launch_sample_tail(E.logits, E.samp_d, d, E.ids_out_d, E.ids_ring_d, B, E.V, E.embed, E.H, E.x,
+                       E.layers[0].attn_norm, E.xb, E.ssq, E.stream);
+  else
+    launch_argmax(E.logits, B, E.V, E.ids_out_d, E.stream);
   E.prof_end(K_MISC);
+  if (samp) return;
   // the next chained step's arguments on the device, then its input rows
   launch_decode_advance(d, E.ids_out_d, E.ids_ring_d, B, E.V, E.stream);
   decode_head(E, B, d);
@@ -1790,7 +1521,7 @@ static void decode_run(ms_engine& E, std::vector<Seq*>& batch, int k, std::vecto
         E.allocs.push_back(p);
       } else {
         (void)hipGetLastError();
-        E.persist = false;
+        E.S.persist = false;
         E.pk_used = false;
       }
     }
@@ -1813,7 +1544,7 @@ static void decode_run(ms_engine& E, std::vector<Seq*>& batch, int k, std::vecto
   da.B = B;
   // the split grid only depends on the longest sequence rounded up to 256 keys
   da.max_len = ((max_len + k - 1 + 255) / 256) * 256;
-  da.ppw = E.attn_ppw;
+  da.ppw = E.S.attn_ppw;
   auto graph = [&](int steps) {  // `steps` chained decode bodies in one graph
     const auto key = std::make_tuple(B, da.max_len, steps, samp ? 1 : 0);
     auto it = E.decode_graphs.find(key);
@@ -1832,8 +1563,8 @@ static void decode_run(ms_engine& E, std::vector<Seq*>& batch, int k, std::vecto
     it->second.second = ++E.graph_clock;
     return it->second.first;
   };
-  if (E.use_graphs && E.prof_mask == 0) {
-    const int G = std::max(1, E.graph_steps);
+  if (E.S.use_graphs && E.prof_mask == 0) {
+    const int G = std::max(1, E.S.graph_steps);
     for (int j = 0; j + G <= k; j += G) HIP_OK(hipGraphLaunch(graph(G), E.stream));
     for (int j = 0; j < k % G; ++j) HIP_OK(hipGraphLaunch(graph(1), E.stream));
   } else {
@@ -1855,7 +1586,7 @@ static void decode_run(ms_engine& E, std::vector<Seq*>& batch, int k, std::vecto
     // is at a position the recomputation writes again
     fprintf(stderr, "mapsum: persistent decode step timed out (code 0x%x); recomputing with the launches\n",
             *E.pk_err_h);
-    E.persist = false;
+    E.S.persist = false;
     E.pk_used = false;
     HIP_OK(hipMemsetAsync(E.pk_sync, 0, persist_sync_words(E.L) * sizeof(unsigned), E.stream));
     HIP_OK(hipMemsetAsync(E.pk_err_d, 0, 4 * sizeof(unsigned), E.stream));
@@ -1877,7 +1608,7 @@ int ms_step(ms_engine* e) {
     ms_engine& E = *e;
     HIP_OK(hipSetDevice(E.cfg.device));
     // Profiling runs serialise the phases, so every bracketed launch runs alone on the chip.
-    const bool ov = E.overlap && E.prof_mask == 0;
+    const bool ov = E.S.overlap && E.prof_mask == 0;
     TraceRange tr_step("mapsum.step");
     // 1. admit (the new slots' block-table rows go out on the prefill stream)
     E.use(E.cp);
@@ -1931,13 +1662,13 @@ int ms_step(ms_engine* e) {
       if (!s->finish && s->len > 0) batch.push_back(s.get());
     for (size_t i0 = 0; i0 < batch.size(); i0 += 256) {
       std::vector<Seq*> sub(batch.begin() + i0, batch.begin() + std::min(batch.size(), i0 + 256));
-      int k = (batch.size() > 256 || (!E.waiting.empty() && !E.free_slots.empty())) ? 1 : E.max_run;
+      int k = (batch.size() > 256 || (!E.waiting.empty() && !E.free_slots.empty())) ? 1 : E.S.max_run;
       // chunks wait for a slot: a chunk that stops at EOS inside the run keeps its slot until
       // the run ends, so bound the run by one captured graph (<= 16 steps) instead of 64
-      if (!E.waiting.empty()) k = std::min(k, std::max(1, E.graph_steps));
+      if (!E.waiting.empty()) k = std::min(k, std::max(1, E.S.graph_steps));
       // a prefill is in flight on the other stream: decode a whole graph of steps under it
       // (a one-step run would leave the prefill exposed)
-      if (ov && !admitted.empty() && batch.size() <= 256) k = std::max(k, std::max(1, E.graph_steps));
+      if (ov && !admitted.empty() && batch.size() <= 256) k = std::max(k, std::max(1, E.S.graph_steps));
       int max_len = 0;
       for (Seq* s : sub) {
         k = std::min(k, s->num_predict - (int)s->out.size());
@@ -2037,7 +1768,7 @@ int ms_set_persist(ms_engine* e, int32_t on) {
   if (!e) return MS_EINVAL;
   return guarded(e, [&]() -> int {
     HIP_OK(hipStreamSynchronize(e->cd.stream));
-    e->persist = on != 0;
+    e->S.persist = on != 0;
     e->drop_graphs();
     return (e->persist_ok ? 1 : 0);
   });
@@ -2063,18 +1794,6 @@ int ms_debug_read(ms_engine* e, int32_t which, int64_t offset, void* host, int64
     HIP_OK(hipMemcpy(host, (const char*)base + offset, (size_t)bytes, hipMemcpyDeviceToHost));
     return MS_OK;
   });
-}
-
-int ms_debug_pk_stamps(uint64_t* out, int32_t n) {
-  if (!out || n < 0) return MS_EINVAL;
-  ms::persist_stamps(reinterpret_cast<unsigned long long*>(out), n);
-  return MS_OK;
-}
-
-int ms_debug_a2_stamps(uint64_t* out, int32_t n) {
-  if (!out || n < 0) return MS_EINVAL;
-  ms::attn2_stamps(reinterpret_cast<unsigned long long*>(out), n);
-  return MS_OK;
 }
 
 int ms_synchronize(ms_engine* e) {
@@ -2141,360 +1860,6 @@ int ms_forward_packed(ms_engine* e, const int32_t* ids, const int32_t* lens, int
 int ms_forward(ms_engine* e, const int32_t* ids, int32_t n, int32_t n_layers_run, float* hidden_out,
                float* logits_out) {
   return ms_forward_packed(e, ids, &n, 1, n_layers_run, hidden_out, logits_out);
-}
-
-// ---------------------------------------------------------------------------- op entry points
-static int op_guard(const std::function<void()>& fn) {
-  try {
-    fn();
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-      g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(err);
-      return MS_EIO;
-    }
-    return MS_OK;
-  } catch (const MsError& x) {
-    g_last_error = x.what();
-    return x.code;
-  }
-}
-
-// the deferred RMSNorm scale the next op calls of this thread apply (ms_op_set_row_scale)
-static thread_local RowScale g_op_rs{};
-
-int ms_op_set_row_scale(const float* ssq, int32_t tiles, int32_t hidden, float eps) {
-  if (ssq && (tiles < 1 || hidden < 1)) return MS_EINVAL;
-  g_op_rs = ssq ? make_row_scale(ssq, tiles, hidden, eps) : RowScale{};
-  return MS_OK;
-}
-
-static int op_rs_tiles() { return g_op_rs.ssq ? g_op_rs.tiles : 0; }
-
-static const GemvArgs* op_gemv_args(GemvArgs& ga) {
-  ga = GemvArgs{};
-  ga.rs = g_op_rs;
-  return g_op_rs.ssq ? &ga : nullptr;
-}
-
-int ms_op_gemm(const void* A, const void* W, void* out, int32_t M, int32_t N, int32_t K, int32_t ldo,
-               int32_t epi, void* stream) {
-  return op_guard([&] {
-    REQUIRE(A && W && out && M >= 1 && N >= 16 && K >= 64 && K % 64 == 0, MS_EINVAL, "bad gemm shape");
-    REQUIRE(((epi >= 0 && epi <= 3) || epi == MS_EPI_ARGMAX) && (epi != MS_EPI_SWIGLU || N % 32 == 0), MS_EINVAL,
-            "bad epilogue");
-    REQUIRE(epi != MS_EPI_ADD_F32 || (N % 4 == 0 && ldo % 4 == 0), MS_EINVAL,
-            "residual gemm: N and ldo multiples of 4 (16-B x rows)");
-    // argmax: {max, id} float2 partials [M][ldo >= N / 16], the 128x128 tile, no row scale
-    REQUIRE(epi != MS_EPI_ARGMAX || (N % 16 == 0 && ldo >= N / 16), MS_EINVAL, "gemm argmax: N % 16, ldo >= N / 16");
-    // the epilogues store 4 consecutive columns per lane (8 B fp16, 16 B fp32)
-    REQUIRE(((uintptr_t)out & ((epi == MS_EPI_ADD_F32 || epi == MS_EPI_STORE_F32) ? 15 : 7)) == 0, MS_EINVAL,
-            "gemm: out must be 16-B (fp32) / 8-B (fp16) aligned");
-    REQUIRE(!g_op_rs.ssq || gemm_rs_tiles_ok(M, N, g_op_rs.tiles), MS_EINVAL,
-            "gemm row scale: at most 24 tiles of statistics (kGemmRsTiles, both GEMM tiles)");
-    launch_gemm((const f16_t*)A, (const f16_t*)W, out, M, N, K, ldo, epi == MS_EPI_ARGMAX ? MS_GEMV_EPI_ARGMAX : epi,
-                (hipStream_t)stream, &g_op_rs);
-  });
-}
-
-int ms_op_gemm_resid(const void* A, const void* W, float* x, void* xg_out, const void* gamma, float* ssq_out,
-                     int32_t M, int32_t N, int32_t K, void* stream) {
-  return op_guard([&] {
-    REQUIRE(A && W && x && xg_out && gamma && ssq_out && M >= 1 && N >= 16 && K >= 64 && K % 64 == 0, MS_EINVAL,
-            "bad gemm_resid operands (K % 64 == 0)");
-    REQUIRE(gemm_resid_tiles(M, N) <= kGemmRsTiles, MS_EINVAL, "gemm_resid: N over 24 column tiles");
-    REQUIRE(N % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)xg_out & 7) == 0, MS_EINVAL,
-            "gemm_resid: N a multiple of 4, x 16-B and xg 8-B aligned (vector rows)");
-    GemmResid gr{(const f16_t*)gamma, (f16_t*)xg_out, ssq_out};
-    launch_gemm((const f16_t*)A, (const f16_t*)W, x, M, N, K, N, MS_EPI_ADD_F32, (hipStream_t)stream, nullptr, &gr);
-  });
-}
-
-int ms_gemm_resid_tiles(int32_t M, int32_t N) { return gemm_resid_tiles(M, N); }
-
-int ms_set_gemm_variant(int32_t v) {
-  if (v < 0 || v > 4) return MS_EINVAL;
-  set_gemm_variant(v);
-  return MS_OK;
-}
-
-int ms_set_gemv_order(int32_t order) {
-  if (order < -1 || order > 2) return MS_EINVAL;
-  set_gemv_order(order);
-  return MS_OK;
-}
-
-int ms_debug_gemv_stamps(uint64_t* out, int32_t n) {
-  if (!out || n < 0) return MS_EINVAL;
-  ms::gemv_stamps(reinterpret_cast<unsigned long long*>(out), n);
-  return MS_OK;
-}
-
-int ms_set_attn_tuning(int32_t combine_grp, int32_t order) {
-  if (combine_grp < 0 || combine_grp > 1 || (order != 0 && order != 3)) return MS_EINVAL;
-  set_attn_tuning(combine_grp, order);
-  return MS_OK;
-}
-
-int ms_set_dgemm_kh(int32_t kh) {
-  if (kh != 1 && kh != 2) return MS_EINVAL;
-  set_dgemm_kh(kh);
-  return MS_OK;
-}
-
-int ms_set_dgemm_wn(int32_t wn) {
-  if (wn != 4 && wn != 8) return MS_EINVAL;
-  set_dgemm_wn(wn);
-  return MS_OK;
-}
-
-int ms_set_qgemv_gs(int32_t on) {
-  if (on < 0 || on > 1) return MS_EINVAL;
-  set_qgemv_gs(on != 0);
-  return MS_OK;
-}
-
-int64_t ms_op_gemv_workspace(int32_t M, int32_t N, int32_t K) {
-  if (M < 1 || M > 64 || N < 16 || K < 64 || K % 64) return MS_EINVAL;
-  return (int64_t)gemv_workspace_bytes(M, N, K);
-}
-
-int ms_op_gemv(const void* X, const void* W, void* out, int32_t M, int32_t N, int32_t K, int32_t ldo,
-               int32_t epi, void* ws, void* stream) {
-  return ms_op_gemv_tuned(X, W, out, M, N, K, ldo, epi, ws, 0, stream);
-}
-
-int ms_op_gemv_tuned(const void* X, const void* W, void* out, int32_t M, int32_t N, int32_t K,
-                     int32_t ldo, int32_t epi, void* ws, int32_t waves, void* stream) {
-  return op_guard([&] {
-    REQUIRE(X && W && out && ws && N >= 16 && N % 16 == 0, MS_EINVAL, "bad gemv operands");
-    REQUIRE(((epi >= 0 && epi <= 3) || epi == MS_EPI_ARGMAX) && (epi != MS_EPI_SWIGLU || N % 32 == 0),
-            MS_EINVAL, "bad epilogue");
-    REQUIRE(gemv_supported(M, N, K, epi, op_rs_tiles()), MS_EINVAL,
-            "gemv shape unsupported (M<=64, K%64==0, K/64 split into <=16 waves of <=8 steps; "
-            "row-scale statistics within kRsStage and LDS)");
-    GemvArgs ga;
-    launch_gemv_ex((const f16_t*)X, (const f16_t*)W, out, M, N, K, ldo, epi, op_gemv_args(ga), waves,
-                   (hipStream_t)stream);
-  });
-}
-
-int ms_op_gemv_strided(const void* X, const void* W, void* out, int32_t M, int32_t N, int32_t K,
-                       int32_t ldk, int32_t ldo, int32_t epi, void* stream) {
-  return op_guard([&] {
-    REQUIRE(X && W && out && N >= 16 && N % 16 == 0 && ldk >= K && ldk % 8 == 0, MS_EINVAL,
-            "bad strided gemv operands");
-    REQUIRE(epi >= 0 && epi <= 3 && epi != MS_EPI_SWIGLU, MS_EINVAL, "bad epilogue");
-    REQUIRE(gemv_supported(M, N, K, epi), MS_EINVAL, "gemv shape unsupported");
-    launch_gemv_strided((const f16_t*)X, (const f16_t*)W, out, M, N, K, ldk, ldo, epi, (hipStream_t)stream);
-  });
-}
-
-int ms_op_gemv_resid(const void* X, const void* W, float* x, void* xg_out, const void* gamma,
-                     float* ssq_out, int32_t M, int32_t N, int32_t K, int32_t rt, void* stream) {
-  return op_guard([&] {
-    // (a ragged last tile is fine: its rows are clamped on load and masked in the epilogue)
-    REQUIRE(X && W && x && xg_out && gamma && ssq_out && rt >= 1 && rt <= 16 && N >= 1, MS_EINVAL,
-            "bad gemv_resid operands");
-    REQUIRE(gemv_supported(M, N, K, MS_GEMV_EPI_RESID_SSQ), MS_EINVAL, "gemv_resid shape unsupported");
-    GemvArgs ga{};
-    ga.rt = rt;
-    ga.ssq_out = ssq_out;
-    ga.gamma = (const f16_t*)gamma;
-    ga.xg_out = (f16_t*)xg_out;
-    launch_gemv_ex((const f16_t*)X, (const f16_t*)W, x, M, N, K, N, MS_GEMV_EPI_RESID_SSQ, &ga, 0,
-                   (hipStream_t)stream);
-  });
-}
-
-int ms_op_dgemm(const void* X, const void* W, void* out, int32_t M, int32_t N, int32_t K, int32_t S,
-                int32_t ldo, int32_t epi, void* stream) {
-  return op_guard([&] {
-    REQUIRE(X && W && out, MS_EINVAL, "bad dgemm operands");
-    REQUIRE(((epi >= 0 && epi <= 3) || epi == MS_EPI_ARGMAX) && dgemm_supported(M, N, K, S, epi), MS_EINVAL,
-            "dgemm shape unsupported (M <= 256, N % 64 == 0, K % (64 S) == 0, S > 1 only for fp32 slabs)");
-    REQUIRE(!g_op_rs.ssq || g_op_rs.tiles == 1, MS_EINVAL, "dgemm row scale: one-tile statistics only");
-    launch_dgemm((const f16_t*)X, (const f16_t*)W, out, M, N, K, S, ldo, epi, (hipStream_t)stream, &g_op_rs);
-  });
-}
-
-int ms_op_gemv_split(const void* X, const void* W, float* slabs, int32_t M, int32_t N, int32_t K,
-                     int32_t S, int32_t waves, void* stream) {
-  return op_guard([&] {
-    REQUIRE(X && W && slabs && N >= 16 && S >= 1, MS_EINVAL, "bad gemv_split operands");
-    REQUIRE(gemv_split_supported(M, N, K, S, op_rs_tiles()), MS_EINVAL,
-            "gemv_split shape unsupported (M<=64, (K/S)%64==0, row-scale statistics within kRsStage and LDS)");
-    GemvArgs ga;
-    launch_gemv_split((const f16_t*)X, (const f16_t*)W, slabs, M, N, K, S, waves, (hipStream_t)stream,
-                      op_gemv_args(ga));
-  });
-}
-
-int ms_op_residual_rmsnorm(float* x, const float* slabs, int32_t S, const void* w, void* y, float* ssq,
-                           int32_t rows, int32_t hidden, void* stream) {
-  return op_guard([&] {
-    REQUIRE(x && w && y && ssq && rows >= 1 && hidden >= 4 && hidden % 4 == 0 && hidden <= 8192, MS_EINVAL,
-            "bad residual_rmsnorm shape");
-    REQUIRE(S == 0 || slabs, MS_EINVAL, "slabs missing");
-    REQUIRE(residual_rmsnorm_supported(S, hidden) || (S == 0 && hidden <= 8192), MS_EINVAL,
-            "residual_rmsnorm: S <= 8 and hidden <= 3072 (wider rows: S == 0 only)");
-    launch_residual_rmsnorm(x, slabs, S, (const f16_t*)w, (f16_t*)y, ssq, rows, hidden,
-                            (hipStream_t)stream);
-  });
-}
-
-int ms_op_dequant(int32_t type, const void* blocks, int64_t n_blocks, float* out, void* stream) {
-  return op_guard([&] {
-    REQUIRE(blocks && out && n_blocks >= 1, MS_EINVAL, "bad dequant arguments");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
-    launch_dequant_f32(type, (const uint8_t*)blocks, n_blocks, out, (hipStream_t)stream);
-  });
-}
-
-int ms_op_quant_rows(int32_t type, const void* blocks, int32_t rows, int32_t K, void* f16_out,
-                     void* packed_out, void* stream) {
-  return op_guard([&] {
-    REQUIRE(blocks && f16_out && rows >= 1 && K >= 256 && K % 256 == 0, MS_EINVAL, "bad quant_rows arguments");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
-    launch_quant_rows(type, (const uint8_t*)blocks, rows, K, (f16_t*)f16_out, 16, 0,
-                      (uint8_t*)packed_out, 0, (hipStream_t)stream);
-  });
-}
-
-int ms_op_qgemv(const void* X, int32_t type, const void* packed, void* out, int32_t M, int32_t N,
-                int32_t K, int32_t ldo, int32_t epi, void* stream) {
-  return op_guard([&] {
-    REQUIRE(X && packed && out && N >= 16, MS_EINVAL, "bad qgemv operands");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
-    REQUIRE(((epi >= 0 && epi <= 3) || epi == MS_EPI_ARGMAX) && (epi != MS_EPI_SWIGLU || N % 32 == 0),
-            MS_EINVAL, "bad epilogue");
-    REQUIRE(qgemv_supported(M, N, K, epi, op_rs_tiles()), MS_EINVAL,
-            "qgemv shape unsupported (M<=64, K%256==0, N%16==0, row-scale statistics within kRsStage and LDS)");
-    QMat q{};
-    q.n = 1;
-    q.base0 = (const uint8_t*)packed;
-    q.row0_0 = 0;
-    q.type0 = type;
-    q.row_bytes0 = (K / 256) * qblock_bytes(type, true);
-    GemvArgs ga;
-    launch_qgemv((const f16_t*)X, q, out, M, N, K, ldo, epi, op_gemv_args(ga), (hipStream_t)stream);
-  });
-}
-
-int ms_op_qgemv_split(const void* X, int32_t type, const void* packed, float* slabs, int32_t M,
-                      int32_t N, int32_t K, int32_t S, void* stream) {
-  return op_guard([&] {
-    REQUIRE(X && packed && slabs && N >= 16 && S >= 1, MS_EINVAL, "bad qgemv_split operands");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
-    REQUIRE(qgemv_split_supported(M, N, K, S, op_rs_tiles()), MS_EINVAL,
-            "qgemv_split shape unsupported (M<=64, K%(256*S)==0, row-scale statistics within kRsStage and LDS)");
-    QMat q{};
-    q.n = 1;
-    q.base0 = (const uint8_t*)packed;
-    q.row0_0 = 0;
-    q.type0 = type;
-    q.row_bytes0 = (K / 256) * qblock_bytes(type, true);
-    GemvArgs ga;
-    launch_qgemv_split((const f16_t*)X, q, slabs, M, N, K, S, (hipStream_t)stream, op_gemv_args(ga));
-  });
-}
-
-int ms_op_qgemv_resid(const void* X, int32_t type, const void* packed, float* x, void* xg_out, const void* gamma,
-                      float* ssq_out, int32_t M, int32_t N, int32_t K, int32_t rt, void* stream) {
-  return op_guard([&] {
-    REQUIRE(X && packed && x && xg_out && gamma && ssq_out && rt >= 1 && rt <= 16 && N % rt == 0, MS_EINVAL,
-            "bad qgemv_resid operands");
-    REQUIRE(qtype_known(type), MS_EINVAL, "ggml type must be Q8_0, Q4_K, Q5_K or Q6_K");
-    REQUIRE(qgemv_supported(M, N, K, MS_GEMV_EPI_RESID_SSQ), MS_EINVAL, "qgemv_resid shape unsupported");
-    QMat q{};
-    q.n = 1;
-    q.base0 = (const uint8_t*)packed;
-    q.row0_0 = 0;
-    q.type0 = type;
-    q.row_bytes0 = (K / 256) * qblock_bytes(type, true);
-    GemvArgs ga{};
-    ga.rt = rt;
-    ga.ssq_out = ssq_out;
-    ga.gamma = (const f16_t*)gamma;
-    ga.xg_out = (f16_t*)xg_out;
-    launch_qgemv((const f16_t*)X, q, x, M, N, K, N, MS_GEMV_EPI_RESID_SSQ, &ga, (hipStream_t)stream);
-  });
-}
-
-int ms_op_qdgemm(const void* X, int32_t type, const void* packed, void* out, int32_t M, int32_t N, int32_t K,
-                 int32_t S, int32_t ldo, int32_t epi, void* stream) {
-  return op_guard([&] {
-    REQUIRE(X && packed && out && N >= 64 && K >= 256 && S >= 1, MS_EINVAL, "bad qdgemm operands");
-    REQUIRE(type != MS_QT_Q8_0, MS_EINVAL,
-            "qdgemm has no Q8_0 form (Q8_0 engines run their fp16 copies in the large regime): Q4_K, Q5_K, Q6_K or F16");
-    REQUIRE(type == MS_QT_Q4_K || type == MS_QT_Q5_K || type == MS_QT_Q6_K || type == 1, MS_EINVAL,
-            "ggml type must be Q4_K, Q5_K, Q6_K or F16");
-    REQUIRE(!g_op_rs.ssq || g_op_rs.tiles == 1, MS_EINVAL, "qdgemm row scale: one-tile statistics only");
-    if (type == 1) {  // fp16 rows [N][K] through the same kernel
-      const int e = epi == MS_EPI_ARGMAX ? MS_GEMV_EPI_ARGMAX : epi;
-      REQUIRE(qdgemm_f16_supported(M, N, K, S, e), MS_EINVAL, "qdgemm (fp16 rows) shape unsupported");
-      launch_qdgemm_f16((const f16_t*)X, (const f16_t*)packed, out, M, N, K, S, ldo, e, (hipStream_t)stream, &g_op_rs);
-      return;
-    }
-    QMat q{};
-    q.n = 1;
-    q.base0 = (const uint8_t*)packed;
-    q.row0_0 = 0;
-    q.type0 = type;
-    q.row_bytes0 = (K / 256) * qblock_bytes(type, true);
-    const int e = epi == MS_EPI_ARGMAX ? MS_GEMV_EPI_ARGMAX : epi;
-    REQUIRE(qdgemm_supported(M, N, K, S, e, q), MS_EINVAL,
-            "qdgemm shape unsupported (M <= 256, N % 64 == 0, K % (256 S) == 0, S > 1 only for fp32 slabs)");
-    launch_qdgemm((const f16_t*)X, q, out, M, N, K, S, ldo, e, (hipStream_t)stream, &g_op_rs);
-  });
-}
-
-int ms_op_rmsnorm(const void* x, const void* w, void* y, float* ssq, int32_t rows, int32_t hidden,
-                  const int32_t* row_idx, void* stream) {
-  return op_guard([&] {
-    REQUIRE(x && w && y && ssq && rows >= 1 && hidden >= 4 && hidden % 4 == 0 && hidden <= 8192, MS_EINVAL,
-            "bad rmsnorm shape");
-    launch_rmsnorm((const float*)x, (const f16_t*)w, (f16_t*)y, ssq, rows, hidden, row_idx,
-                   (hipStream_t)stream);
-  });
-}
-
-int ms_op_argmax_partials(const void* partials, int32_t rows, int32_t tiles, int32_t* ids, void* stream) {
-  return op_guard([&] {
-    REQUIRE(partials && ids && rows >= 1 && tiles >= 1, MS_EINVAL, "bad argmax_partials shape");
-    launch_argmax_partials(partials, rows, tiles, ids, (hipStream_t)stream);
-  });
-}
-
-int ms_op_sample(const float* logits, int32_t rows, int32_t n, int64_t ldl, const ms_sampling* params,
-                 const int32_t* win, const int32_t* win_len, const int32_t* steps, int32_t* ids,
-                 int32_t* cand_ids, float* cand_p, int32_t* cand_n, void* stream) {
-  return op_guard([&] {
-    REQUIRE(logits && params && win && win_len && steps && ids && rows >= 1, MS_EINVAL, "bad sample operands");
-    REQUIRE(n >= 1 && n <= kSampleMaxN && ldl >= n, MS_EINVAL,
-            "bad sample shape (1 <= n <= " + std::to_string(kSampleMaxN) + ", ldl >= n)");
-    REQUIRE((cand_ids && cand_p && cand_n) || (!cand_ids && !cand_p && !cand_n), MS_EINVAL,
-            "sample: the candidate outputs come together");
-    SampleArgs a{};
-    a.logits = logits;
-    a.ldl = ldl;
-    a.n = n;
-    a.params = reinterpret_cast<const SampleParams*>(params);
-    a.win = win;
-    a.win_len = win_len;
-    a.steps = steps;
-    a.ids_out = ids;
-    a.cand_ids = cand_ids;
-    a.cand_p = cand_p;
-    a.cand_n = cand_n;
-    launch_sample_rows(a, rows, (hipStream_t)stream);
-  });
-}
-
-int ms_op_argmax(const void* logits, int32_t rows, int32_t n, int32_t* ids, void* stream) {
-  return op_guard([&] {
-    REQUIRE(logits && ids && rows >= 1 && n >= 1, MS_EINVAL, "bad argmax shape");
-    launch_argmax((const float*)logits, rows, n, ids, (hipStream_t)stream);
-  });
 }
 
 }  // extern "C"

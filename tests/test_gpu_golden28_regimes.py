@@ -1,17 +1,27 @@
 """All 28 layers in the decode regimes the product actually runs (needs a GPU).
 
 tests/test_gpu_golden28.py checks the benchmarked 8-slot engine.  An engine's decode
-arithmetic is fixed at ms_create from max_batch (include/mapsum.h):
+arithmetic is fixed at ms_create from max_batch; the one function that ranks the kernel families
+is pick_form (csrc/decode_forms.h), its table is in DESIGN.md §5, and tests/test_decode_forms.py
+pins that table on the CPU.  fp16 engines:
    1-16 slots  GEMV, O / down with the residual + statistics epilogue (the 8-slot bench);
   17-23 slots  GEMV, split-K O / down + residual_rmsnorm                  -> 20 slots here;
    >=24 slots  skinny GEMM (k_dgemm.hip), 8 KV pages per attention wave  -> 64 slots (the
                drop-in default, compat.py MAPSUM_MAX_BATCH) and 128 slots (configs[2]);
    >=96 slots  the same, with the lm_head's greedy partials on the prefill GEMM's 128x128
-               tile                                                       -> 128 and 256 slots
-               (256: 16-row-tile skinny GEMMs, the configs[2] record's width);
-and K-quant engines (configs[4], Q4_K_M) keep the exact Q-GEMV at every size: <= 16 slots
-with the residual epilogue, above that in row groups of <= 64 rows with split-K O / down
--> 8 and 128 slots here.  The reference hands the engine every chunk at once
+               tile                                                       -> 128 and 256 slots;
+  >=192 slots  the projections on the skinny GEMM's fp16-rows form (k_qdgemm.hip), QKV / down
+               split 3 / 4                                                -> 256 slots (the
+               configs[2] record's width);
+and K-quant engines (configs[4], Q4_K_M):
+   1-16 slots  the exact Q-GEMV, O / down with the residual epilogue      -> 8 slots here;
+  17-64 slots  the exact Q-GEMV, split-4 O / down + residual_rmsnorm (not run here);
+   >=65 slots  the K-quant skinny GEMM (k_qdgemm.hip) on the packed rows of all-Q4_K matrices,
+               whose values are the fp16 copy's; Q6_K and mixed matrices on their fp16 copies
+               through k_dgemm.hip; from 96 slots the lm_head (Q6_K) on the 128x128 tile
+               -- so the numerics change across the 64 / 65 boundary        -> 128 slots here;
+  >=192 slots  the same with QKV / down split 3 / 4 (not run here; the CPU table pins the choice).
+The reference hands the engine every chunk at once
 (runners/run_summarization_ollama_mapreduce.py:109-112), so large engines are the normal
 case of the replaced call (run_full_evaluation_pipeline.py:80-106).
 
