@@ -254,4 +254,16 @@ inline Form pick_form(const DecodeSettings& s, const DecodeMat& m, const FormCal
   return {F_GEMV, S >= 1 && S <= kMaxSplit && gemv_split_supported(M, N, K, S) ? S : 1, true};
 }
 
+// Decode attention's split grid.  A run of k chained steps launches one grid, set from its longest
+// sequence at the run's last step rounded UP to 256 keys, so the grid (and the captured graph) only
+// changes at multiples of 256; ms_step bounds k so that a run never crosses one (decode_run_cap).
+// When max_ctx is no multiple of 256 the grid passes max_ctx: the v1 / v2 partial workspaces and
+// the persistent step's partial stride are sized for attn_ws_ctx(max_ctx), the longest grid an
+// engine can launch (tests/native/decode_forms.cpp sweeps every reachable length against them).
+inline int attn_ws_ctx(int max_ctx) { return (max_ctx + 255) / 256 * 256; }
+inline int decode_grid_len(int max_len, int k) { return ((max_len + k - 1 + 255) / 256) * 256; }
+inline int decode_run_cap(int max_len) { return ((max_len + 255) / 256) * 256 - max_len + 1; }
+// v2's splits over a grid of grid_len keys (ppb pages per block), as launch_attn_decode2 counts them
+inline int attn2_nsplit(int grid_len, int ppb) { return ((grid_len + kPage - 1) / kPage + ppb - 1) / ppb; }
+
 }  // namespace ms

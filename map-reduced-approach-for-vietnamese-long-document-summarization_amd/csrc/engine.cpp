@@ -352,7 +352,7 @@ struct ms_engine {
              dgemm_supported(B, H, Hq * D, S.dsplit_o, MS_GEMV_EPI_STORE_F32, 1) &&
              dgemm_supported(B, H, F, S.dsplit_down, MS_GEMV_EPI_STORE_F32, 1) &&
              dgemm_supported(B, 2 * F, H, 1, MS_GEMV_EPI_SWIGLU, S.dgemm_kh) && (2 * F) % 32 == 0 &&
-             attn_decode_supported(B, Hq, Hk, max_pages * kPage);
+             attn_decode_supported(B, Hq, Hk, max_pages * kPage, S.attn_ppw);
     // row groups (K-quant engines above 64 rows): split-K slabs and SwiGLU only, no residual
     // epilogue (resid_fused is off in large engines), one residual_rmsnorm over all rows
     if (S.row_groups(B) && !(B <= kMaxSlabRows && S.attn_slabs && !S.resid_fused(nullptr))) return false;
@@ -366,7 +366,7 @@ struct ms_engine {
            gemv_split_supported(Bg, H, Hq * D, 1) && gemv_split_supported(Bg, H, F, 1) &&
            (!S.resid_fuse || (gemv_supported(Bg, H, Hq * D, MS_GEMV_EPI_RESID_SSQ) &&
                               gemv_supported(Bg, H, F, MS_GEMV_EPI_RESID_SSQ))) &&
-           attn_decode_supported(B, Hq, Hk, max_pages * kPage);
+           attn_decode_supported(B, Hq, Hk, max_pages * kPage, S.attn_ppw);
   }
   // a row group's deferred-norm scale: one-tile statistics are per row ([M]), so the group
   // starts at its first row (multi-tile [tiles][M] statistics never reach row groups)
@@ -731,7 +731,7 @@ int ms_create(const ms_config* cfg, ms_engine** out) {
     // decode_run sets the split grid from the longest sequence rounded UP to 256 keys, which can
     // pass max_ctx when max_ctx is not a multiple of 256: size both attention
     // workspaces for the rounded context
-    const int ws_ctx = (cfg->max_ctx + 255) / 256 * 256;
+    const int ws_ctx = attn_ws_ctx(cfg->max_ctx);
     E.attn_ws = (float*)E.dalloc<char>(std::max(attn_decode_workspace_bytes(cfg->max_batch, E.Hq, ws_ctx),
                                                 attn_decode2_workspace_bytes(cfg->max_batch, E.Hq, ws_ctx,
                                                                              E.S.attn_ppb)),
@@ -752,8 +752,7 @@ int ms_create(const ms_config* cfg, ms_engine** out) {
       int dev_cu = 0;
       HIP_OK(hipDeviceGetAttribute(&dev_cu, hipDeviceAttributeMultiprocessorCount, cfg->device));
       E.n_cu = dev_cu;
-      const int np_ws = (ws_ctx + kPage - 1) / kPage;
-      E.nsplit_ws = (np_ws + E.S.attn_ppb - 1) / E.S.attn_ppb;
+      E.nsplit_ws = attn2_nsplit(ws_ctx, E.S.attn_ppb);
       E.persist_ok = persist_supported(cfg->max_batch, E.H, E.F, E.Hq, E.Hk, E.D, E.L, E.S.attn_ppb, E.n_cu) &&
                      E.slot_major && E.S.attn_v2 && E.S.resid_rt == 12;
       E.pk_sync = E.dalloc<unsigned>(persist_sync_words(E.L), true);
@@ -1543,7 +1542,7 @@ static void decode_run(ms_engine& E, std::vector<Seq*>& batch, int k, std::vecto
   da.seq_slot = d + 2 * (size_t)B;
   da.B = B;
   // the split grid only depends on the longest sequence rounded up to 256 keys
-  da.max_len = ((max_len + k - 1 + 255) / 256) * 256;
+  da.max_len = decode_grid_len(max_len, k);
   da.ppw = E.S.attn_ppw;
   auto graph = [&](int steps) {  // `steps` chained decode bodies in one graph
     const auto key = std::make_tuple(B, da.max_len, steps, samp ? 1 : 0);
@@ -1675,7 +1674,7 @@ int ms_step(ms_engine* e) {
         if (!s->forced.empty()) k = 1;  // the next input is the forced id, not this step's choice
         max_len = std::max(max_len, s->len + 1);
       }
-      k = std::max(1, std::min(k, ((max_len + 255) / 256) * 256 - max_len + 1));
+      k = std::max(1, std::min(k, decode_run_cap(max_len)));
       std::vector<int32_t> ids;
       {
         TraceRange tr("mapsum.decode_run");

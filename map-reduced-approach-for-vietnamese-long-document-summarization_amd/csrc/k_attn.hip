@@ -347,9 +347,11 @@ constexpr int kMaxSlabs = 8;    // QKV split-K slabs (engine kMaxSplit)
 // fold, RoPE) and epilogue (merge, partial) are paid once per 36 pages instead of per 8.
 // MS_ATTN_PPW pins ppw (tuning).
 constexpr int kTargetBlocks = 512, kMaxPPW = 16;
+// read when an engine is created (its ppw and its workspace), like MS_ATTN_PPB: tests pin several
+// values in one process; no launch reads it (attn_decode_supported takes the engine's ppw)
 static int decode_ppw_env() {
-  static const int v = [] { const char* e = getenv("MS_ATTN_PPW"); return e ? atoi(e) : 0; }();
-  return v;
+  const char* e = getenv("MS_ATTN_PPW");
+  return e ? atoi(e) : 0;
 }
 int attn_decode_ppw(int max_batch, int Hk, int max_ctx) {
   const int np = (max_ctx + kPage - 1) / kPage;
@@ -365,6 +367,7 @@ static int decode_nsplit(int ppw, int max_len) {
   const int np = (max_len + kPage - 1) / kPage;
   return (np + kSplitPages * ppw - 1) / (kSplitPages * ppw);
 }
+int attn_decode_nsplit(int ppw, int max_len) { return decode_nsplit(ppw, max_len); }
 // the most splits any B can get (ppw >= 1 under MS_ATTN_PPW, else >= 2)
 static int decode_nsplit_max(int max_len) {
   const int np = (max_len + kPage - 1) / kPage;
@@ -379,9 +382,10 @@ size_t attn_decode_workspace_bytes(int B, int Hq, int max_len) {
   return (size_t)B * Hq * decode_nsplit_max(max_len) * 132 * sizeof(float);
 }
 
-bool attn_decode_supported(int B, int Hq, int Hk, int max_len) {
+bool attn_decode_supported(int B, int Hq, int Hk, int max_len, int ppw) {
   (void)B;
-  return Hk >= 1 && Hq % Hk == 0 && Hq / Hk <= kMaxGroup && decode_nsplit_max(max_len) <= kMaxSplits;
+  const int nsplit = ppw > 0 ? decode_nsplit(ppw, max_len) : decode_nsplit_max(max_len);
+  return Hk >= 1 && Hq % Hk == 0 && Hq / Hk <= kMaxGroup && nsplit <= kMaxSplits;
 }
 
 // PPWT = 2: the page loop unrolled for exactly 2 pages per wave (the B = 8 plan); 0: runtime
@@ -725,10 +729,10 @@ static void launch_combine(const float* ws, f16_t* out, int B, int Hq, int Hk, i
 void launch_attn_decode(const DecodeQKV& qa, f16_t* out, int Hq, int Hk, KVView kv,
                         DecodeAttnArgs a, float* ws, hipStream_t s) {
   if (a.B <= 0) return;
-  if (!attn_decode_supported(a.B, Hq, Hk, a.max_len)) return;  // callers check
+  const int ppw = a.ppw > 0 ? a.ppw : 2;
+  if (!attn_decode_supported(a.B, Hq, Hk, a.max_len, ppw)) return;  // callers check
   if (qa.slabs && (qa.S < 1 || qa.S > kMaxSlabs)) return;
   if (qa.slabs && qa.rs.ssq && (qa.rs.tiles < 1 || qa.rs.tiles > 256)) return;  // callers check
-  const int ppw = a.ppw > 0 ? a.ppw : 2;
   const int nsplit = decode_nsplit(ppw, a.max_len);
   const float scale_log2 = kLog2e / sqrtf((float)kHeadDim);
   const dim3 grid(a.B, Hk, nsplit);

@@ -338,10 +338,15 @@ struct DecodeQKV {
 };
 // split partials of decode attention (combined by a second launch)
 size_t attn_decode_workspace_bytes(int B, int Hq, int max_len);
-bool attn_decode_supported(int B, int Hq, int Hk, int max_len);
+// ppw: the pages per wave the launch will use (an engine's attn_decode_ppw); 0: the fewest any
+// engine can get under the current MS_ATTN_PPW, as the workspace is sized
+bool attn_decode_supported(int B, int Hq, int Hk, int max_len, int ppw = 0);
 // pages per wave of an engine's decode attention (from its max_batch / max_ctx, never from
 // one step's batch: the split boundaries set a sequence's summation order)
 int attn_decode_ppw(int max_batch, int Hk, int max_ctx);
+// splits of a launch over a grid of max_len keys at ppw pages per wave (4 waves per block): the
+// partials of a launch take B * Hq * attn_decode_nsplit * 132 floats of the workspace
+int attn_decode_nsplit(int ppw, int max_len);
 void launch_attn_decode(const DecodeQKV& qa, f16_t* out, int Hq, int Hk, KVView kv,
                         DecodeAttnArgs a, float* ws, hipStream_t s);
 // one page per wave, ppb waves per block (k_attn.hip "v2"): pages per block fixed per engine

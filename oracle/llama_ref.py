@@ -113,8 +113,13 @@ class OracleLlama:
 
     MODES = ("engine", "bf16", "fp32", "f16")
 
-    def __init__(self, cfg, weights: dict, mode: str = "engine"):
-        """Numerics mode:
+    def __init__(self, cfg, weights: dict, mode: str = "engine", acc=np.float32):
+        """``acc``: the accumulation dtype.  float32 (default) is numpy's own fp32 matmul; with
+        float64 every matmul, the RMSNorm sum of squares and the softmax row sum accumulate in
+        float64 and are rounded to fp32 once, at the same rounding points -- the distance between
+        the two is the summation-order noise of the contract (tests/decode_edges_ref.py).
+
+        Numerics mode:
 
         * ``"engine"`` (default) -- the HIP engine's fp16 contract (module docstring, DESIGN.md
           §2): weights held as fp16 (exact for bf16-valued weights), the rounding points below
@@ -137,17 +142,34 @@ class OracleLlama:
         assert self.mode in self.MODES, self.mode
         if self.mode in ("f16", "engine"):
             weights = _f16_weights(weights)
+        self.acc = np.dtype(acc)
+        assert self.acc in (np.dtype(np.float32), np.dtype(np.float64)), acc
+        if self.acc == np.float64:  # exact copies: the products and sums are what widens
+            wide = lambda d: {k: (v.astype(np.float64) if isinstance(v, np.ndarray) and v.ndim == 2 else v)
+                              for k, v in d.items()}
+            tied = weights["lm_head"] is weights["embed"]
+            layers = [wide(L) for L in weights["layers"]]
+            weights = wide({k: v for k, v in weights.items() if k != "layers"})
+            weights["layers"] = layers
+            if tied:
+                weights["lm_head"] = weights["embed"]
         self.w = weights
         self.rnd = {"engine": _f16, "bf16": bf16_rne, "fp32": _f32, "f16": _f16}[self.mode]
 
     def new_cache(self):
         return {"k": [None] * self.cfg.n_layers, "v": [None] * self.cfg.n_layers, "len": 0}
 
-    def forward(self, ids, cache=None, collect: bool = False, all_logits: bool = False):
+    def forward(self, ids, cache=None, collect: bool = False, all_logits: bool = False, mut=None):
         """Run ``ids`` after whatever ``cache`` holds; returns (logits, probes).
 
         logits: [T, vocab] if all_logits else [vocab] for the last token.
-        probes: per-layer residual after each layer (if collect)."""
+        probes: per-layer residual after each layer (if collect).
+
+        ``mut`` (tests only: deliberately wrong references, tests/decode_edges_ref.py) is a dict
+        of optional callables: ``"new_kv"(layer, k, v) -> (k, v)`` replaces the new tokens' RoPE
+        (k [T, Hk, D] arrives rounded but un-roped; what it returns is cached and attended), and
+        ``"attend"(layer, k, v) -> (k, v)`` edits the [S, Hk, D] keys and values this call attends
+        to without touching the cache (one new token only: the causal mask is not re-derived)."""
         cfg, w = self.cfg, self.w
         ids = np.asarray(ids, dtype=np.int64)
         T = ids.shape[0]
@@ -161,58 +183,76 @@ class OracleLlama:
         rnd = self.rnd
         f16 = self.mode == "f16"
         eps = cfg.norm_eps
+        wide = self.acc == np.float64
+        mut = mut or {}
+        self.last_rinv = None  # the final norm's row factor: logits / last_rinv = the unscaled lm_head sums
+
+        def mm(a, b):
+            """a @ b accumulated in self.acc, returned as fp32."""
+            if wide:
+                return np.matmul(a.astype(np.float64), b.astype(np.float64)).astype(np.float32)
+            return np.matmul(a, b)
+
+        def rinv(x):
+            return rms_rinv_f64(x, eps) if wide else rms_rinv(x, eps)
 
         def normed(x, g):
             """(GEMM input, per-row factor applied after the GEMM)."""
             if f16:  # ggml: rms_norm then mul by g in fp32, the matmul rounds its input
                 return _f16((x * rms_rinv_f64(x, eps)) * g), np.float32(1.0)
             if self.mode == "engine":  # kernels.h kXgScale: f16(x g 2^-4), 16 r -- exact scalings
-                return rnd((x * g).astype(np.float32) * np.float32(0.0625)), rms_rinv(x, eps) * np.float32(16.0)
-            return norm_input(x, g, rnd), rms_rinv(x, eps)
+                return rnd((x * g).astype(np.float32) * np.float32(0.0625)), rinv(x) * np.float32(16.0)
+            return norm_input(x, g, rnd), rinv(x)
 
         pre = _f32 if f16 else rnd  # Q/K/V before RoPE: ggml keeps them fp32
         x = w["embed"][ids].astype(np.float32)
         probes = []
         for l, L in enumerate(w["layers"]):
             xg, r = normed(x, L["attn_norm"])
-            q = pre(r * (xg @ L["wq"].T)).reshape(T, Hq, D)
-            k = pre(r * (xg @ L["wk"].T)).reshape(T, Hk, D)
-            v = rnd(r * (xg @ L["wv"].T)).reshape(T, Hk, D)
+            q = pre(r * mm(xg, L["wq"].T)).reshape(T, Hq, D)
+            k = pre(r * mm(xg, L["wk"].T)).reshape(T, Hk, D)
+            v = rnd(r * mm(xg, L["wv"].T)).reshape(T, Hk, D)
             q = apply_rope(q, cos, sin, rnd)  # f16: Q rounded for K.Q, K for the F16 cache
-            k = apply_rope(k, cos, sin, rnd)
+            if "new_kv" in mut:
+                k, v = mut["new_kv"](l, k, v)
+            else:
+                k = apply_rope(k, cos, sin, rnd)
             if cache["k"][l] is not None:
                 k = np.concatenate([cache["k"][l], k], axis=0)
                 v = np.concatenate([cache["v"][l], v], axis=0)
             cache["k"][l], cache["v"][l] = k, v
+            if "attend" in mut:
+                k, v = mut["attend"](l, k, v)
             S = k.shape[0]
             kq = np.repeat(k, G, axis=1)  # [S, Hq, D]
             vq = np.repeat(v, G, axis=1)
-            s = np.matmul(q.transpose(1, 0, 2), kq.transpose(1, 2, 0)) * scale  # [Hq, T, S]
+            s = mm(q.transpose(1, 0, 2), kq.transpose(1, 2, 0)) * scale  # [Hq, T, S]
             mask = (np.arange(S)[None, :] > (p0 + np.arange(T))[:, None])
             s = np.where(mask[None], np.float32(-np.inf), s)
             s = s - s.max(axis=-1, keepdims=True)
             p = np.exp(s)
-            den = p.sum(axis=-1, keepdims=True)
+            den = p.sum(axis=-1, keepdims=True, dtype=self.acc).astype(np.float32)
             if self.mode == "engine":  # flash kernels: fp16(p) . V, then / the fp32 row sum
-                pv = np.matmul(_f16(p), vq.transpose(1, 0, 2)) / den
+                pv = mm(_f16(p), vq.transpose(1, 0, 2)) / den
             else:
                 p = p / den
                 if f16:  # V.P: ggml rounds the fp32 probabilities to the F16 V's vec_dot type
                     p = _f16(p)
-                pv = np.matmul(p.astype(np.float32), vq.transpose(1, 0, 2))
+                pv = mm(p.astype(np.float32), vq.transpose(1, 0, 2))
             o = rnd(pv.transpose(1, 0, 2))  # [T, Hq, D]
-            x = x + o.reshape(T, Hq * D) @ L["wo"].T
+            x = x + mm(o.reshape(T, Hq * D), L["wo"].T)
             xg, r = normed(x, L["ffn_norm"])
-            g = r * (xg @ L["w_gate"].T)
-            u = r * (xg @ L["w_up"].T)
+            g = r * mm(xg, L["w_gate"].T)
+            u = r * mm(xg, L["w_up"].T)
             h = rnd(silu(g) * u)
-            x = x + h @ L["w_down"].T
+            x = x + mm(h, L["w_down"].T)
             if collect:
                 probes.append(x.copy())
         cache["len"] = p0 + T
         xs = x if all_logits else x[-1:]
         xg, r = normed(xs, w["final_norm"])
-        logits = r * (xg @ w["lm_head"].T)
+        logits = r * mm(xg, w["lm_head"].T)
+        self.last_rinv = r
         return (logits if all_logits else logits[0]), probes
 
     def generate(self, ids, num_predict: int, eos_ids=(), ignore_eos: bool = False):

@@ -7,7 +7,15 @@
 // engine makes -- for the kernel family and split of QKV, O, gate/up, down and the lm_head (greedy
 // and sampling) of every regime DESIGN.md §5 lists, and compares them with the table below.
 // Quantised engines are QMat type fields filled by hand: no device pointers.
+//
+// It also sweeps the decode-attention workspaces (sweep_workspaces below): for every engine shape,
+// MS_ATTN_PPB / MS_ATTN_PPW setting, reachable context length and run length, the split grid that
+// decode_run launches (decode_forms.h decode_grid_len) must fit what ms_create allocates
+// (attn_ws_ctx) -- the grid is rounded up to 256 keys and passes max_ctx when max_ctx is not a
+// multiple of 256.
+#include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -98,6 +106,60 @@ static void expect(const char* what, const Eng& e, const char* const (&want)[6])
   std::printf("\n");
 }
 
+// the partials of one launch: (row, q head, split) x 132 floats (k_attn.hip)
+static size_t partial_bytes(int B, int Hq, int nsplit) { return (size_t)B * Hq * nsplit * 132 * sizeof(float); }
+
+static void env_or_unset(const char* name, int v) {
+  if (v > 0) setenv(name, std::to_string(v).c_str(), 1);
+  else unsetenv(name);
+}
+
+// Every launch of decode attention an engine can make, against the engine's allocation.  ms_create
+// sizes one workspace, max(v1, v2) bytes at attn_ws_ctx(max_ctx), and the persistent step's
+// partial stride nsplit_ws; decode_run launches a grid of decode_grid_len(max_len, k) keys, where
+// max_len = the longest sequence + its new token (2 .. max_ctx) and k <= min(64, decode_run_cap)
+// steps that stay inside max_ctx.  ppb / ppw: the engine's own choice and every pinned value.
+static void sweep_workspaces() {
+  const int Hq = 24, Hk = 8;
+  long checked = 0, bad = 0;
+  for (int ppw_env = 0; ppw_env <= 16; ++ppw_env) {
+    env_or_unset("MS_ATTN_PPW", ppw_env);
+    for (int ppb_env : {0, 4, 5, 6, 7, 8, 9}) {
+      env_or_unset("MS_ATTN_PPB", ppb_env);
+      for (int mb : {1, 6, 8, 16, 24, 128, 256})
+        for (int ctx : {64, 100, 1000, 1600, 2304, 4100}) {
+          const int ppw = attn_decode_ppw(mb, Hk, ctx), ppb = attn_decode2_ppb(mb, Hk, ctx);
+          const int ws_ctx = attn_ws_ctx(ctx), nsplit_ws = attn2_nsplit(ws_ctx, ppb);
+          const size_t ws = std::max(attn_decode_workspace_bytes(mb, Hq, ws_ctx),
+                                     attn_decode2_workspace_bytes(mb, Hq, ws_ctx, ppb));
+          bool ok = (ppw_env == 0 || ppw == ppw_env) && (ppb_env == 0 || ppb == ppb_env) &&
+                    partial_bytes(mb, Hq, nsplit_ws) <= ws;  // the persistent step's stride
+          for (int len = 2; len <= ctx; ++len) {
+            const int kmax = std::min({64, decode_run_cap(len), ctx - len + 1});
+            for (int k = 1; k <= kmax; ++k, ++checked) {
+              const int grid = decode_grid_len(len, k);
+              const int n2 = attn2_nsplit(grid, ppb), n1 = attn_decode_nsplit(ppw, grid);
+              ok = ok && grid >= len + k - 1 && n2 <= nsplit_ws && partial_bytes(mb, Hq, n2) <= ws &&
+                   partial_bytes(mb, Hq, n1) <= ws;
+            }
+          }
+          if (!ok) {
+            ++bad;
+            std::printf("workspace too small: max_batch %d max_ctx %d ppb %d ppw %d\n", mb, ctx, ppb, ppw);
+          }
+        }
+    }
+  }
+  unsetenv("MS_ATTN_PPW");
+  unsetenv("MS_ATTN_PPB");
+  // the sweep can fail: sized for max_ctx itself (as before the rounding fix), a 1600-key engine at
+  // 9 pages per block has 3 splits' room and launches 4 (the grid is 1792 keys)
+  const bool teeth = attn2_nsplit(decode_grid_len(1591, 1), 9) > attn2_nsplit(1600, 9);
+  fails += (int)bad + !teeth;
+  std::printf("workspace sweep: %ld launches checked, %ld engine shapes too small%s\n", checked, bad,
+              teeth ? "" : ", and the un-rounded sizing passes (it must not)");
+}
+
 int main() {
   std::printf("%-34s QKV O gate/up down lm_head(greedy) lm_head(sampling)\n", "engine");
   // fp16: GEMV with the residual epilogue up to 16 slots, split-K + residual_rmsnorm above; the
@@ -131,6 +193,7 @@ int main() {
   e.s.qlarge_min = 129;
   fails += !(e.s.row_groups(128) && !e.s.large());
   expect("Q4_K_M 128, MS_QLARGE_MIN=129", e, {"QGEMV/4", "QGEMV/4", "QGEMV", "QGEMV/4", "QGEMV", "QGEMV"});
+  sweep_workspaces();
   std::printf("%s: %d mismatch(es)\n", fails ? "DECODE_FORMS_FAIL" : "DECODE_FORMS_OK", fails);
   return fails ? 1 : 0;
 }

@@ -5,6 +5,11 @@ pick_form (csrc/decode_forms.h) is the one function that ranks the kernel famili
 data and the launchers' *_supported predicates -- host code that needs no device.  The standalone
 tests/native/decode_forms.cpp asks it with the engine's own calls and compares the answers with
 its table; this test links that program against the built objects (`make forms`) and runs it.
+
+The same program sweeps the decode-attention workspaces: every split grid decode_run can launch
+(decode_forms.h decode_grid_len: rounded up to 256 keys, past max_ctx when that is no multiple of
+256) against the bytes and the partial stride ms_create allocates, for every MS_ATTN_PPB /
+MS_ATTN_PPW setting, engine shape, reachable context length and run length.
 """
 import os
 import subprocess
@@ -26,3 +31,4 @@ def test_decode_regime_table():
     print(r.stdout)
     print(r.stderr[-3000:])
     assert r.returncode == 0 and "DECODE_FORMS_OK" in r.stdout
+    assert "workspace sweep:" in r.stdout and " 0 engine shapes too small" in r.stdout
