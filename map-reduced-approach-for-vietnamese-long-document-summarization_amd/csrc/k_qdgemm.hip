@@ -18,39 +18,21 @@
 //    same kernel on fp16 rows, kQdF16, runs gate/up at M = 128 in 33.7 us against 29.0 us on
 //    Q4_K; profiles/r06/v10_*);
 //  * W: one super-block (256 k) of the wave's 16 rows per ring slot, DPF super-blocks in flight
-//    (Q4_K: header + sub-blocks 0-3 / 4-7, 48 B per lane; Q5_K: the same and the lane group's 8 qh
-//    bytes; Q6_K: four 8-B ql pieces, two 8-B qh pieces, the scales and d);
+//    (the packed layouts and each format's per-lane register image and fetch: qblock.h);
 //  * MFMA column c of a super-block (v_mfma_f32_16x16x32_f16, 32 consecutive k): lane group g
-//    holds k = 32c + 8g .. +7 of its row -- the packed Q4_K layout's own order (quant_rows_kernel)
-//    and Q6_K's natural one -- and reads the same k of X;
-//  * dequant: Q4_K / Q5_K y = fma(d*sc, q, -(dmin*m)) (the products are exact in fp32 -- 11 + 6 + 5
-//    bits at most -- so this is ggml's d1*q - m1 with its single rounding), Q6_K y = fma(d*sc, q, -32 d*sc) (ggml's
-//    (d*sc)*(q-32)), both rounded to fp16 by v_cvt_pk_f16_f32 (RNE, as the fp16 copy);
+//    holds k = 32c + 8g .. +7 of its row -- the packed Q4_K layout's own order and Q6_K's natural
+//    one -- and reads the same k of X;
+//  * dequant (qblock.h kq_dequant / q6_dequant): ggml's d1*q - m1 and (d*sc)*(q-32) as one fma each,
+//    with ggml's single rounding, then rounded to fp16 by v_cvt_pk_f16_f32 (RNE, as the fp16 copy);
 //  * epilogues as the skinny GEMM: fp32 split-K slabs (gridDim.y), SwiGLU on the 16-row
 //    interleaved gate/up rows, greedy argmax partials; the rows' deferred-norm scale.
 // A row's sum order depends only on (K, split), never on M: batch-invariant inside the regime.
-#include "gemv_common.h"
+#include "qblock.h"
 
 namespace ms {
 
 constexpr int QBK = 64;  // k per X stage: two 32-k MFMA columns
 
-__device__ __forceinline__ float qd_h2f(uint32_t h16) {
-  return (float)__builtin_bit_cast(_Float16, (uint16_t)(h16 & 0xFFFFu));
-}
-
-struct QdQ4 {  // one packed Q4_K super-block of this lane's row: header, sub-blocks 0-3, 4-7
-  uint4 h, q0, q1;
-};
-struct QdQ5 {  // one packed Q5_K super-block: Q4_K's three pieces and qh[8g .. 8g + 7]
-  uint4 h, q0, q1;
-  uint2 qh;
-};
-struct QdQ6 {  // one packed Q6_K super-block: ql pieces [k4 & 1][n], qh [n], scales, d
-  uint2 ql[2][2], qh[2];
-  uint4 sc;
-  uint32_t d;
-};
 // fp16 rows through the same kernel (the large regime's fp16 projections): 256 k = 512 B of a row,
 // MFMA column c's 8 weights of lane group g at 64 c + 16 g
 constexpr int kQdF16 = 1;  // ggml_type F16
@@ -58,98 +40,23 @@ struct QdH {
   uint4 w[8];
 };
 
-__device__ __forceinline__ uint32_t qd_word(const uint4& v, int i) {
-  return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
-}
-
 // W loads: plain loads the compiler tracks (its own waits cover each ring slot's first use).
 // Every byte a fetch loads is used, so none is dropped or narrowed and each fetch issues exactly
-// kQdLoads instructions -- the counts the step waits assume (checked in the ISA).
-__device__ __forceinline__ uint4 qd_ld16(const uint8_t* p) { return ldw16(p); }
-__device__ __forceinline__ uint2 qd_ld8(const uint8_t* p) { return *(const uint2*)p; }
-__device__ __forceinline__ uint32_t qd_ld4(const uint8_t* p) { return *(const uint32_t*)p; }
-
-__device__ __forceinline__ void qd_fetch(QdQ4& r, const uint8_t* bp, int g) {
-  r.h = qd_ld16(bp);
-  r.q0 = qd_ld16(bp + 16 + 16 * g);
-  r.q1 = qd_ld16(bp + 80 + 16 * g);
-}
-__device__ __forceinline__ void qd_fetch(QdQ5& r, const uint8_t* bp, int g) {
-  r.h = qd_ld16(bp);
-  r.q0 = qd_ld16(bp + 16 + 16 * g);
-  r.q1 = qd_ld16(bp + 80 + 16 * g);
-  r.qh = qd_ld8(bp + 144 + 8 * g);
-}
+// kQdLoads instructions -- the counts the step waits assume (checked in the ISA).  The register
+// images and fetches of the packed blocks are qblock.h's (KqRegs, Q5Regs, Q6ColRegs).
+__device__ __forceinline__ void qd_fetch(KqRegs& r, const uint8_t* bp, int g) { kq_fetch(r, bp, g); }
+__device__ __forceinline__ void qd_fetch(Q5Regs& r, const uint8_t* bp, int g) { kq_fetch(r, bp, g); }
+__device__ __forceinline__ void qd_fetch(Q6ColRegs& r, const uint8_t* bp, int g) { q6_fetch(r, bp, g); }
 __device__ __forceinline__ void qd_fetch(QdH& r, const uint8_t* bp, int g) {
 #pragma unroll
-  for (int c = 0; c < 8; ++c) r.w[c] = qd_ld16(bp + 64 * c + 16 * g);
-}
-__device__ __forceinline__ void qd_fetch(QdQ6& r, const uint8_t* bp, int g) {
-  // packed 224-B block (quant_rows_kernel): raw ql[n*64 + half*32 + l] at half*64 + 32n + 8g + i
-  // for l = 8g + i; qh and the scales unmoved
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) r.ql[h][n] = qd_ld8(bp + h * 64 + 32 * n + 8 * g);
-#pragma unroll
-  for (int n = 0; n < 2; ++n) r.qh[n] = qd_ld8(bp + 128 + 32 * n + 8 * g);
-  r.sc = qd_ld16(bp + 192);
-  r.d = qd_ld4(bp + 208);
-}
-
-typedef float qd_f2 __attribute__((ext_vector_type(2)));
-
-// four weights held as the bytes of q4 -> two packed fp16 pairs of fma(a, q, b)
-__device__ __forceinline__ void qd_deq4(uint32_t q4, float a, float b, uint32_t& p0, uint32_t& p1) {
-  const qd_f2 a2 = {a, a}, b2 = {b, b};
-  const qd_f2 y01 = __builtin_elementwise_fma(a2, qd_f2{(float)(q4 & 0xFFu), (float)((q4 >> 8) & 0xFFu)}, b2);
-  const qd_f2 y23 = __builtin_elementwise_fma(a2, qd_f2{(float)((q4 >> 16) & 0xFFu), (float)(q4 >> 24)}, b2);
-  p0 = pack2h(y01.x, y01.y);
-  p1 = pack2h(y23.x, y23.y);
+  for (int c = 0; c < 8; ++c) r.w[c] = ldw16(bp + 64 * c + 16 * g);
 }
 
 // the fp16 weights k = 32c + 8g .. +7 of this lane's row (MFMA column c of the super-block)
-__device__ __forceinline__ f16x8 qd_dequant(const QdQ4& r, int c, int g) {
-  (void)g;
-  const int sh = 8 * (c & 3);
-  const uint32_t scw = c < 4 ? (r.h.y & 0x3F3F3F3Fu) : ((r.h.w & 0x0F0F0F0Fu) | ((r.h.y >> 2) & 0x30303030u));
-  const uint32_t mw = c < 4 ? (r.h.z & 0x3F3F3F3Fu) : (((r.h.w >> 4) & 0x0F0F0F0Fu) | ((r.h.z >> 2) & 0x30303030u));
-  const float d1 = __fmul_rn(qd_h2f(r.h.x), (float)((scw >> sh) & 0xFFu));       // ggml d1 = d * sc
-  const float m1 = __fmul_rn(qd_h2f(r.h.x >> 16), (float)((mw >> sh) & 0xFFu));  // ggml m1 = dmin * m
-  const uint32_t qw = qd_word(c < 4 ? r.q0 : r.q1, c & 3);  // byte i = q[k_i] | q[k_{i+4}] << 4
-  uint32_t pk[4];
-  qd_deq4(qw & 0x0F0F0F0Fu, d1, -m1, pk[0], pk[1]);
-  qd_deq4((qw >> 4) & 0x0F0F0F0Fu, d1, -m1, pk[2], pk[3]);
-  return __builtin_bit_cast(f16x8, pk);
-}
-// Q5_K: Q4_K's scales and nibbles; bit c of qh[8g + i] is the fifth bit of weight 32c + 8g + i
-__device__ __forceinline__ f16x8 qd_dequant(const QdQ5& r, int c, int g) {
-  (void)g;
-  const int sh = 8 * (c & 3);
-  const uint32_t scw = c < 4 ? (r.h.y & 0x3F3F3F3Fu) : ((r.h.w & 0x0F0F0F0Fu) | ((r.h.y >> 2) & 0x30303030u));
-  const uint32_t mw = c < 4 ? (r.h.z & 0x3F3F3F3Fu) : (((r.h.w >> 4) & 0x0F0F0F0Fu) | ((r.h.z >> 2) & 0x30303030u));
-  const float d1 = __fmul_rn(qd_h2f(r.h.x), (float)((scw >> sh) & 0xFFu));
-  const float m1 = __fmul_rn(qd_h2f(r.h.x >> 16), (float)((mw >> sh) & 0xFFu));
-  const uint32_t qw = qd_word(c < 4 ? r.q0 : r.q1, c & 3);
-  uint32_t pk[4];
-  qd_deq4((qw & 0x0F0F0F0Fu) | (((r.qh.x >> c) & 0x01010101u) << 4), d1, -m1, pk[0], pk[1]);
-  qd_deq4(((qw >> 4) & 0x0F0F0F0Fu) | (((r.qh.y >> c) & 0x01010101u) << 4), d1, -m1, pk[2], pk[3]);
-  return __builtin_bit_cast(f16x8, pk);
-}
-__device__ __forceinline__ f16x8 qd_dequant(const QdH& r, int c, int g) {
-  (void)g;
-  return __builtin_bit_cast(f16x8, r.w[c]);
-}
-__device__ __forceinline__ f16x8 qd_dequant(const QdQ6& r, int c, int g) {
-  const int n = c >> 2, k4 = c & 3;  // weights n*128 + k4*32 + l, l = 8g + i
-  const float ds = __fmul_rn(qd_h2f(r.d), (float)(int)(int8_t)((qd_word(r.sc, 2 * n + (k4 >> 1)) >> (8 * ((g >> 1) + 2 * (k4 & 1)))) & 0xFFu));
-  const uint2 a = r.ql[k4 & 1][n], hq = r.qh[n];
-  const int ns = 4 * (k4 >> 1), hs = 2 * k4;
-  uint32_t pk[4];
-  qd_deq4(((a.x >> ns) & 0x0F0F0F0Fu) | (((hq.x >> hs) & 0x03030303u) << 4), ds, -32.0f * ds, pk[0], pk[1]);
-  qd_deq4(((a.y >> ns) & 0x0F0F0F0Fu) | (((hq.y >> hs) & 0x03030303u) << 4), ds, -32.0f * ds, pk[2], pk[3]);
-  return __builtin_bit_cast(f16x8, pk);
-}
+__device__ __forceinline__ f16x8 qd_dequant(const KqRegs& r, int c, int) { return kq_dequant(r, c); }
+__device__ __forceinline__ f16x8 qd_dequant(const Q5Regs& r, int c, int) { return kq_dequant(r, c); }
+__device__ __forceinline__ f16x8 qd_dequant(const Q6ColRegs& r, int c, int g) { return q6_dequant(r, c, g); }
+__device__ __forceinline__ f16x8 qd_dequant(const QdH& r, int c, int) { return __builtin_bit_cast(f16x8, r.w[c]); }
 
 // the counted waits below hold only if every W load sits where the source puts it, between the
 // step's X DMA and its wait: a memory clobber no load may cross (W is not __restrict__: a
@@ -205,9 +112,9 @@ __device__ __forceinline__ const uint8_t* qd_row(const QdSrc& s, int r) {
 }
 
 template <int QT> struct QdRegs;
-template <> struct QdRegs<MS_QT_Q4_K> { using T = QdQ4; static constexpr int kBytes = kQ4KBytes; };
-template <> struct QdRegs<MS_QT_Q5_K> { using T = QdQ5; static constexpr int kBytes = kQ5KBytes; };
-template <> struct QdRegs<MS_QT_Q6_K> { using T = QdQ6; static constexpr int kBytes = kQ6KPacked; };
+template <> struct QdRegs<MS_QT_Q4_K> { using T = KqRegs; static constexpr int kBytes = kQ4KBytes; };
+template <> struct QdRegs<MS_QT_Q5_K> { using T = Q5Regs; static constexpr int kBytes = kQ5KBytes; };
+template <> struct QdRegs<MS_QT_Q6_K> { using T = Q6ColRegs; static constexpr int kBytes = kQ6KPacked; };
 template <> struct QdRegs<kQdF16> { using T = QdH; static constexpr int kBytes = 512; };
 
 // DPF: super-blocks of W in flight per wave, a divisor of the split's super-block count (the

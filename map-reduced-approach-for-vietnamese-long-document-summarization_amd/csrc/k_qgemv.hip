@@ -1,99 +1,51 @@
-// k_qgemv.hip -- ggml K-quant weights on gfx950: bit-exact dequantisation and the
-// dequant-fused decode GEMV (BASELINE.json config 5).
+// k_qgemv.hip -- ggml K-quant and Q8_0 weights on gfx950: bit-exact dequantisation, the loader's
+// packing kernel and the dequant-fused decode GEMV (BASELINE.json config 5).
 //
 // Ollama's default llama3.2:3b is Q4_K_M: Q4_K (144 B / 256 weights) for most matrices,
-// Q6_K (210 B / 256 weights) for some (EXT: llama.cpp).  The dequantisers restate
-// llama.cpp's dequantize_row_q4_K / _q6_K (oracle/ggml_quants.c) with the non-contracted
-// float forms  y = d1*q - m1  and  y = (d*sc)*q  (__fmul_rn/__fsub_rn), so the fp32 result
-// is bit-identical to the C restatement.
+// Q6_K (210 B / 256 weights) for some (EXT: llama.cpp); the q5_K_M / q5_K_S / q4_K_S mixes add Q5_K,
+// llama3.2:3b-instruct-q8_0 is Q8_0 throughout.  The dequantisers restate llama.cpp's
+// dequantize_row_q4_K / _q5_K / _q6_K / _q8_0 (oracle/ggml_quants.c) with the non-contracted float
+// forms  y = d1*q - m1,  y = (d*sc)*q  and  y = d*q  (__fmul_rn/__fsub_rn), so the fp32 result is
+// bit-identical to the C restatement.
 //
 // Storage (engine.cpp): every quantised matrix keeps both
 //   * a fp16 copy = f16(dequant(blocks)) in the fused row layout, for prefill GEMMs
 //     and the embedding gather (compute-bound; fp16 is what MFMA consumes), and
-//   * the quantised rows for decode, which is HBM-bound: 4.5 / 6.56 bits per weight
-//     instead of 16.  Q4_K blocks keep their 16-B ggml header (d, dmin, 12 scale bytes) and
-//     144 B, but the 128 quant bytes are re-ordered so that lane group g of a wave reads one
-//     dword per sub-block s holding weights 32s+8g .. +7 (byte i = q[k_i] | q[k_{i+4}] << 4),
-//     sub-blocks 0-3 of the 4 groups in 64 contiguous bytes, then 4-7; Q6_K blocks are repacked to 224 B [ql 128 | qh 64 | scales
-//     16 | d 2 + pad] so every field is 16-B aligned, the ql bytes regrouped so that a wave
-//     load reads 64 contiguous bytes per row (quant_rows_kernel).
+//   * the quantised rows for decode, which is HBM-bound: 4.5 / 5.5 / 6.56 / 8.5 bits per weight
+//     instead of 16, repacked by quant_rows_kernel so that one wave load instruction reads 64
+//     contiguous bytes of each row.  The packed layouts, the per-lane register images and the
+//     fragment arithmetic are stated once, in qblock.h.
 // The fused GEMV streams the blocks HBM -> VGPR (one super-block of 256 weights per row
 // per wave-step) and feeds v_mfma_f32_16x16x32_f16:
 //   * Q4_K, one MFMA per 32-weight sub-block: the nibbles become the fp16 subnormals q 2^-24
-//     by a byte permute (exact; gfx950 MFMA keeps fp16 denormal operands), the MFMA gives
-//     A_s = 2^-24 sum_k x_k q_k, and sum_k x_k y_k = (2^24 d_s) A_s - m_s X_s with d_s = d*sc_s,
-//     m_s = dmin*m_s (ggml's
-//     fp32 d1 / m1) and X_s = sum of the sub-block's x (one more MFMA, against ones, shared
-//     by the weight tiles of the block) -- 2 FMAs per output
+//     by a byte permute, the MFMA gives A_s = 2^-24 sum_k x_k q_k, and sum_k x_k y_k =
+//     (2^24 d_s) A_s - m_s X_s with ggml's fp32 d1 / m1 and X_s = sum of the sub-block's x (one
+//     more MFMA, against ones, shared by the weight tiles of the block) -- 2 FMAs per output
 //     element per sub-block instead of dequantising every weight: the decode GEMV uses the
 //     exact fp32 dequantised weights (no fp16 rounding of them, and no cancellation: a
 //     1024 + q bias form cost ~7e-6 relative against fp64);
-//   * Q6_K, dequantised in registers to the fp16 values of the fp16 copy.
-//
-// Q8_0 (ggml type 8, llama3.2:3b-instruct-q8_0) is the third weight form, counted in the same
-// 256-weight units: 8 consecutive ggml blocks {fp16 d; int8 qs[32]} = 272 raw bytes, y = d * q
-// (one fp32 multiply, exact: 11 x 8 significant bits).  Packed unit, 272 B, 16-B aligned:
-//   bytes 0..15                       the 8 fp16 scales d_0 .. d_7 in block order
-//   byte 16 + 64(s>>1) + 16g + 8(s&1) + i = q[32s + 8g + i]   (block s, lane group g, i < 8)
-// so load c of lane group g (16 B at 16 + 64c + 16g) holds its 8 weights of blocks 2c and
-// 2c + 1, and one wave load instruction reads 64 contiguous bytes of each row.  The GEMV runs one
-// MFMA per 32-weight block on q held as the exact fp16 integers -128 .. 127 (byte ^ 0x80 placed
-// under the exponent byte 0x64 is the fp16 1024 + (q + 128); one packed fp16 subtract of 1152
-// gives q, exact), A_b = sum_k x_k q_k, then acc = fma(d_b, A_b, acc) in fp32: the weights are
-// never rounded to fp16, out = sum_b d_b (sum_k x_k q_k).
-//
-// Q5_K (ggml type 13; the q5_K_M / q5_K_S / q4_K_S mixes) is Q4_K with a fifth bit per weight: raw
-// block {fp16 d, dmin; scales[12]; qh[32]; qs[128]} = 176 B, weight t = 32s + l has the code
-// q = nibble(t) + 16 ((qh[l] >> s) & 1) in 0..31 and y = d1*q - m1 with Q4_K's d1, m1.  Packed
-// block, 176 B, 16-B aligned:
-//   bytes 0..15     the header as is
-//   bytes 16..143   the nibbles in Q4_K's packed order (byte 16 + 64(s>>2) + 16g + 4(s&3) + i =
-//                   nib(k) | nib(k+4) << 4, k = 32s + 8g + i, i < 4)
-//   bytes 144..175  qh in its raw order: lane group g reads the 8 bytes at 144 + 8g as two dwords
-//                   Hlo, Hhi; sub-block s's fifth bits are ((H >> s) & 0x01010101) << 4, or-ed into
-//                   the low / high nibble words ahead of Q4_K's byte permute
-// The GEMV is Q4_K's, sum order included: a 5-bit code is still an exact fp16 subnormal q 2^-24.
-// Matrices with a Q5_K region run the QF = MS_QT_Q5_K instantiations (regions Q4_K / Q5_K / Q6_K
-// chosen at run time); matrices without one keep the QF = 0 instantiations unchanged.
+//   * Q5_K: Q4_K's, sum order included -- a 5-bit code is still an exact fp16 subnormal q 2^-24;
+//   * Q6_K, dequantised in registers to the fp16 values of the fp16 copy;
+//   * Q8_0, one MFMA per 32-weight block on q held as the exact fp16 integers -128 .. 127,
+//     A_b = sum_k x_k q_k, then acc = fma(d_b, A_b, acc) in fp32: the weights are never rounded
+//     to fp16, out = sum_b d_b (sum_k x_k q_k).
 #include <algorithm>
 #include <cstdlib>
 
-#include "gemv_common.h"
+#include "qblock.h"
 
 namespace ms {
 
-__device__ __forceinline__ float h2f_lo(uint32_t h16) {
-  return (float)__builtin_bit_cast(_Float16, (uint16_t)(h16 & 0xFFFFu));
-}
-
-__device__ __forceinline__ uint32_t byte_of(const uint4& v, int i) {  // i compile-time or not
-  const uint32_t w = (i < 4) ? v.x : (i < 8) ? v.y : (i < 12) ? v.z : v.w;
-  return (w >> (8 * (i & 3))) & 0xFFu;
-}
-
-// get_scale_min_k4 on the 12 scale bytes = header bytes 4..15 (v.y, v.z, v.w)
-__device__ __forceinline__ void scale_min_k4(const uint4& hdr, int j, int& d, int& m) {
-  auto q = [&](int i) { return (int)byte_of(hdr, 4 + i); };
-  if (j < 4) {
-    d = q(j) & 63;
-    m = q(j + 4) & 63;
-  } else {
-    d = (q(j + 4) & 0xF) | ((q(j - 4) >> 6) << 4);
-    m = (q(j + 4) >> 4) | ((q(j) >> 6) << 4);
-  }
-}
-
 // ---------------------------------------------------------------- dequantisers
 // one 256-thread block per super-block, thread t -> weight t (the C loop order)
-__device__ __forceinline__ float deq_q4k_one(const uint8_t* b, int t) {
-  const uint4 hdr = *(const uint4*)b;
-  const float d = h2f_lo(hdr.x), dmin = h2f_lo(hdr.x >> 16);
-  const int c = t >> 6, w = t & 63, h = w >> 5, l = w & 31;
-  int sc, m;
-  scale_min_k4(hdr, 2 * c + h, sc, m);
-  const uint32_t qb = b[16 + c * 32 + l];
-  const uint32_t q = h ? (qb >> 4) : (qb & 0xF);
-  const float d1 = __fmul_rn(d, (float)sc), m1 = __fmul_rn(dmin, (float)m);
+// raw Q4_K {d, dmin, scales[12], qs[128]} / Q5_K {.., qh[32], qs[128]}: weight t = 32 s + l of sub-block s
+__device__ __forceinline__ float deq_kq_one(const uint8_t* b, int t, bool q5) {
+  const int s = t >> 5, l = t & 31;
+  float d1, m1;
+  kq_scale_min(*(const uint4*)b, s, d1, m1);
+  const uint32_t qb = b[(q5 ? kQ5RawQs : kQ4RawQs) + (t >> 6) * 32 + l];
+  uint32_t q = (s & 1) ? (qb >> 4) : (qb & 0xF);
+  if (q5) q += (((uint32_t)b[kQ5RawQh + l] >> s) & 1u) << 4;
   return __fsub_rn(__fmul_rn(d1, (float)q), m1);
 }
 
@@ -101,38 +53,24 @@ __device__ __forceinline__ float deq_q4k_one(const uint8_t* b, int t) {
 __device__ __forceinline__ float deq_q6k_one(const uint8_t* b, int t) {
   const int n = t >> 7, r = t & 127, k4 = r >> 5, l = r & 31;
   const uint32_t a = b[n * 64 + l + ((k4 & 1) ? 32 : 0)];
-  const uint32_t hb = b[128 + n * 32 + l];
+  const uint32_t hb = b[kQ6Qh + n * 32 + l];
   const int q = (int)(((k4 >> 1) ? (a >> 4) : (a & 0xF)) | (((hb >> (2 * k4)) & 3) << 4)) - 32;
-  const int sc = (int)(int8_t)b[192 + n * 8 + (l >> 4) + 2 * k4];
-  const float d = h2f_lo((uint32_t)b[208] | ((uint32_t)b[209] << 8));
+  const int sc = (int)(int8_t)b[kQ6Sc + n * 8 + (l >> 4) + 2 * k4];
+  const float d = h2f_lo((uint32_t)b[kQ6D] | ((uint32_t)b[kQ6D + 1] << 8));
   return __fmul_rn(__fmul_rn(d, (float)sc), (float)q);
 }
 
 // raw unit of 8 ggml Q8_0 blocks {fp16 d; int8 qs[32]}: weight t is element t & 31 of block t >> 5
 __device__ __forceinline__ float deq_q8_one(const uint8_t* b, int t) {
-  const uint8_t* blk = b + 34 * (t >> 5);
+  const uint8_t* blk = b + kQ8RawBlock * (t >> 5);
   const float d = h2f_lo((uint32_t)blk[0] | ((uint32_t)blk[1] << 8));
   return __fmul_rn(d, (float)(int)(int8_t)blk[2 + (t & 31)]);
 }
 
-// raw ggml Q5_K block: d, dmin, scales[12], qh[32], qs[128]; weight t of sub-block s = t >> 5
-__device__ __forceinline__ float deq_q5k_one(const uint8_t* b, int t) {
-  const uint4 hdr = *(const uint4*)b;
-  const float d = h2f_lo(hdr.x), dmin = h2f_lo(hdr.x >> 16);
-  const int s = t >> 5, l = t & 31, c = t >> 6;
-  int sc, m;
-  scale_min_k4(hdr, s, sc, m);
-  const uint32_t qb = b[48 + c * 32 + l];
-  const uint32_t q = ((t & 32) ? (qb >> 4) : (qb & 0xF)) + ((((uint32_t)b[16 + l] >> s) & 1u) << 4);
-  const float d1 = __fmul_rn(d, (float)sc), m1 = __fmul_rn(dmin, (float)m);
-  return __fsub_rn(__fmul_rn(d1, (float)q), m1);
-}
-
 __device__ __forceinline__ float deq_one(int type, const uint8_t* b, int t) {
-  return type == MS_QT_Q4_K   ? deq_q4k_one(b, t)
-         : type == MS_QT_Q5_K ? deq_q5k_one(b, t)
-         : type == MS_QT_Q8_0 ? deq_q8_one(b, t)
-                              : deq_q6k_one(b, t);
+  return type == MS_QT_Q4_K || type == MS_QT_Q5_K ? deq_kq_one(b, t, type == MS_QT_Q5_K)
+         : type == MS_QT_Q8_0                     ? deq_q8_one(b, t)
+                                                  : deq_q6k_one(b, t);
 }
 
 __global__ __launch_bounds__(256) void dequant_f32_kernel(int type, const uint8_t* __restrict__ blocks,
@@ -147,7 +85,7 @@ void launch_dequant_f32(int type, const uint8_t* blocks, int64_t n_blocks, float
   MS_LAUNCH(dequant_f32_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, type, blocks, out);
 }
 
-// rows of raw blocks -> (a) fp16 rows of the fused matrix, (b) packed quantised rows
+// rows of raw blocks -> (a) fp16 rows of the fused matrix, (b) packed quantised rows (qblock.h's layouts)
 __global__ __launch_bounds__(256) void quant_rows_kernel(int type, const uint8_t* __restrict__ blocks,
                                                          int K, f16_t* __restrict__ dst_f16,
                                                          int map_mul, int map_add,
@@ -163,49 +101,30 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(int type, const uint8_t
     const int bp = qblock_bytes(type, true);
     uint8_t* q = dst_q + ((drow - q_row_base) * nsb + sb) * bp;
     if (type == MS_QT_Q8_0) {
-      // the 8 scales, then quant byte 16 + 64(s >> 1) + 16g + 8(s & 1) + i = q[32s + 8g + i]: lane
-      // group g's weights of blocks 2c, 2c + 1 in one 16-B load at 16 + 64c + 16g (file header)
-      if (t < 16) q[t] = b[34 * (t >> 1) + (t & 1)];
+      if (t < 16) q[kQ8Sc + t] = b[kQ8RawBlock * (t >> 1) + (t & 1)];
       const int s_ = t >> 5, g = (t >> 3) & 3, i = t & 7;
-      q[16 + 64 * (s_ >> 1) + 16 * g + 8 * (s_ & 1) + i] = b[34 * s_ + 2 + (t & 31)];
-    } else if (type == MS_QT_Q4_K) {
-      // header as is; quant byte 16 + 64(s >> 2) + 16g + 4(s & 3) + i = q[k] | q[k + 4] << 4,
-      // k = 32s + 8g + i: lane group g's sub-blocks 0-3 at 16 + 16g, 4-7 at 80 + 16g, so one wave
-      // load instruction reads 64 contiguous bytes of each row
-      if (t < 16) q[t] = b[t];
+      q[kQ8Q + 64 * (s_ >> 1) + 16 * g + 8 * (s_ & 1) + i] = b[kQ8RawBlock * s_ + 2 + (t & 31)];
+    } else if (type == MS_QT_Q4_K || type == MS_QT_Q5_K) {
+      // header as is; the nibbles from the raw qs (Q5_K's sit behind its qh); Q5_K's qh unmoved in value
+      const int qs = type == MS_QT_Q5_K ? kQ5RawQs : kQ4RawQs;
+      if (t < 16) q[kKqHdr + t] = b[t];
       if (t < 128) {
         const int g = t >> 5, s_ = (t >> 2) & 7, i = t & 3;
         auto nib = [&](int k) {
-          const uint32_t qb = b[16 + (k >> 6) * 32 + (k & 31)];
+          const uint32_t qb = b[qs + (k >> 6) * 32 + (k & 31)];
           return ((k & 63) >> 5) ? (qb >> 4) : (qb & 0xF);
         };
         const int k = 32 * s_ + 8 * g + i;
-        q[16 + 64 * (s_ >> 2) + 16 * g + 4 * (s_ & 3) + i] = (uint8_t)(nib(k) | (nib(k + 4) << 4));
-      }
-    } else if (type == MS_QT_Q5_K) {
-      // header as is, the nibbles (raw qs at byte 48) in Q4_K's packed order, qh unmoved in value:
-      // raw 16 + l -> 144 + l (file header)
-      if (t < 16) q[t] = b[t];
-      if (t < 128) {
-        const int g = t >> 5, s_ = (t >> 2) & 7, i = t & 3;
-        auto nib = [&](int k) {
-          const uint32_t qb = b[48 + (k >> 6) * 32 + (k & 31)];
-          return ((k & 63) >> 5) ? (qb >> 4) : (qb & 0xF);
-        };
-        const int k = 32 * s_ + 8 * g + i;
-        q[16 + 64 * (s_ >> 2) + 16 * g + 4 * (s_ & 3) + i] = (uint8_t)(nib(k) | (nib(k + 4) << 4));
-      } else if (t < 160) {
-        q[144 + (t - 128)] = b[16 + (t - 128)];
+        q[(s_ < 4 ? kKqNib0 : kKqNib1) + 16 * g + 4 * (s_ & 3) + i] = (uint8_t)(nib(k) | (nib(k + 4) << 4));
+      } else if (type == MS_QT_Q5_K && t < 160) {
+        q[kQ5Qh + (t - 128)] = b[kQ5RawQh + (t - 128)];
       }
     } else {
-      // Q6_K: same fields (qh at 128, scales at 192, d at 208, tail padded), ql regrouped by the
-      // GEMV's lane group g = 2 hh + p: its low-half 16 bytes (raw hh*64 + 16p ..) at 16g and its
-      // high-half 16 bytes (raw hh*64 + 32 + 16p ..) at 64 + 16g -- one wave load instruction
-      // then reads 64 contiguous bytes of each row (one 64-B line) instead of two half lines
-      // (qh is already in that order: raw 128 + hh*32 + 16p = 128 + 16g)
+      // Q6_K: ql regrouped by the GEMV's lane group g = 2 hh + p, the other fields where they were,
+      // the tail zeroed
       if (t < 128) {
         const int hh = t >> 6, half = (t >> 5) & 1, p = (t >> 4) & 1, i = t & 15;
-        q[half * 64 + 16 * (2 * hh + p) + i] = b[t];
+        q[(half ? kQ6Ql1 : kQ6Ql0) + 16 * (2 * hh + p) + i] = b[t];
       } else if (t < braw) {
         q[t] = b[t];
       }
@@ -229,6 +148,17 @@ __device__ __forceinline__ uint64_t smix(uint64_t z) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
+__device__ __forceinline__ void put_f16(uint8_t* p, _Float16 v) {
+  const uint16_t u = __builtin_bit_cast(uint16_t, v);
+  p[0] = u & 0xFF;
+  p[1] = u >> 8;
+}
+// the K-quant header's d and dmin = ratio * d (of the rounded d)
+__device__ __forceinline__ void put_d_dmin(uint8_t* b, float d, float ratio) {
+  const _Float16 dh = (_Float16)d;
+  put_f16(b, dh);
+  put_f16(b + 2, (_Float16)((float)dh * ratio));
+}
 
 __global__ void synth_qblocks_kernel(int type, uint8_t* __restrict__ blocks, int64_t n_blocks,
                                      uint64_t seed_h, float scale) {
@@ -243,32 +173,23 @@ __global__ void synth_qblocks_kernel(int type, uint8_t* __restrict__ blocks, int
     }
     const float u = 0.5f + (float)(smix(h) >> 40) * (1.0f / 16777216.0f);
     if (type == MS_QT_Q4_K) {
-      const _Float16 d = (_Float16)(u * scale / 270.f);
-      const _Float16 dm = (_Float16)((float)d * 7.5f);
-      const uint16_t db = __builtin_bit_cast(uint16_t, d), dmb = __builtin_bit_cast(uint16_t, dm);
-      b[0] = db & 0xFF; b[1] = db >> 8; b[2] = dmb & 0xFF; b[3] = dmb >> 8;
+      put_d_dmin(b, u * scale / 270.f, 7.5f);
     } else if (type == MS_QT_Q5_K) {
       // sc, m uniform on 0..63 and q on 0..31: dmin = 15.5 d centres y / d = sc q - 15.5 m, whose
       // variance is E[sc^2] E[q^2] - (E[sc] E[q])^2 + 15.5^2 Var(m) = 434054 - 238388 + 81985, std 527;
       // with u on [0.5, 1.5) (rms 1.041) the weights have std ~ scale for d = u scale / 548
-      const _Float16 d = (_Float16)(u * scale / 548.f);
-      const _Float16 dm = (_Float16)((float)d * 15.5f);
-      const uint16_t db = __builtin_bit_cast(uint16_t, d), dmb = __builtin_bit_cast(uint16_t, dm);
-      b[0] = db & 0xFF; b[1] = db >> 8; b[2] = dmb & 0xFF; b[3] = dmb >> 8;
+      put_d_dmin(b, u * scale / 548.f, 15.5f);
     } else if (type == MS_QT_Q8_0) {
       // uniform int8 quants have std 73.9; the 8 blocks' scales spread over [0.5, 1.5) scale / 74
       // (std of the weights 1.04 scale), positive normal fp16 for any scale >= 5e-3
       uint64_t hs = smix(h ^ 0x51ull);
       for (int k = 0; k < 8; ++k) {
         const float uk = 0.5f + (float)((hs >> (8 * k)) & 0xFF) * (1.0f / 256.0f);
-        const uint16_t db = __builtin_bit_cast(uint16_t, (_Float16)(uk * scale / 74.f));
-        b[34 * k] = db & 0xFF; b[34 * k + 1] = db >> 8;
+        put_f16(b + kQ8RawBlock * k, (_Float16)(uk * scale / 74.f));
       }
     } else {
-      for (int k = 0; k < 16; ++k) b[192 + k] = (uint8_t)((int)(b[192 + k] & 0x7F) - 64);
-      const _Float16 d = (_Float16)(u * scale / 680.f);
-      const uint16_t db = __builtin_bit_cast(uint16_t, d);
-      b[208] = db & 0xFF; b[209] = db >> 8;
+      for (int k = 0; k < 16; ++k) b[kQ6Sc + k] = (uint8_t)((int)(b[kQ6Sc + k] & 0x7F) - 64);
+      put_f16(b + kQ6D, (_Float16)(u * scale / 680.f));
     }
   }
 }
@@ -280,60 +201,47 @@ void launch_synth_qblocks(int type, uint8_t* blocks, int64_t n_blocks, uint64_t 
 }
 
 // ---------------------------------------------------------------- dequant-fused GEMV
-// one packed Q8_0 unit of this lane's row: the 8 scales and lane group g's four 16-B quant pieces
-struct Q8Regs {
-  uint4 sc, q[4];
-};
-// tile: the block-uniform address of the tile's first row (a scalar base for the loads); row, sb:
-// this lane's row in the tile and unit in the row (a 32-bit lane offset)
-__device__ __forceinline__ void q8_fetch(Q8Regs& r, const uint8_t* tile, int row_bytes, int row, int sb, int g) {
-  const uint32_t o = (uint32_t)(row * row_bytes + sb * kQ8Bytes);
-  const uint8_t* qp = tile + (o + 16u + 16u * (uint32_t)g);  // one 32-bit lane offset per address
-  r.sc = ldw16(tile + o);
-#pragma unroll
-  for (int c = 0; c < 4; ++c) r.q[c] = ldw16(qp + 64 * c);
-}
-// the same in two halves (the grid-stride loop's prefetch): the scales and blocks 0-3, blocks 4-7.
-// Here the tile is a 32-bit byte offset from the matrix base (the launcher checks the matrix is
-// < 4 GiB): scalar base + 32-bit lane offsets, where 64-bit lane addresses carried across the
-// loop (4 VGPRs) spilled
-template <int HALF>
-__device__ __forceinline__ void q8_fetch_half(Q8Regs& r, const uint8_t* base, uint32_t tile, int row_bytes, int row, int sb,
-                                              int g) {
-  const uint32_t o = tile + (uint32_t)(row * row_bytes + sb * kQ8Bytes);
-  const uint8_t* qp = base + (o + 16u + 16u * (uint32_t)g);
-  if constexpr (HALF == 0) r.sc = ldw16(base + o);
-#pragma unroll
-  for (int c = 2 * HALF; c < 2 * HALF + 2; ++c) r.q[c] = ldw16(qp + 64 * c);
-}
-__device__ __forceinline__ float q8_scale(const Q8Regs& r, int s) {  // s compile-time
-  const uint32_t w = (s >> 1) == 0 ? r.sc.x : (s >> 1) == 1 ? r.sc.y : (s >> 1) == 2 ? r.sc.z : r.sc.w;
-  return h2f_lo(w >> (16 * (s & 1)));
-}
-// block s's 8 int8 weights of this lane group as the exact fp16 integers: byte ^ 0x80 under the
-// exponent byte 0x64 is the fp16 1024 + (q + 128) (perm selector 4 = byte 0 of the constant),
-// and 1024 + (q + 128) - 1152 = q with no rounding (q = -128: 1024 - 1152)
-__device__ __forceinline__ f16x8 q8_frag(const Q8Regs& r, int s) {  // s compile-time
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+// What qgemv_kernel and the grid-stride kernels share: each format's register image, fetch and
+// code -> fragment functions (qblock.h), so a Q6_K tile is q6_frag in both.  The Q4_K / Q5_K and the
+// Q8_0 multiply-accumulate are stated twice: kq_mac below serves the grid-stride gate/up kernel, and
+// qgemv_kernel's two branches and the Q8_0 grid-stride loop write the same statements inline, because
+// any shared function in those loop bodies moved the register allocation of spilling SwiGLU
+// instantiations (the branches say which; profiles/qblock/README.md).  tests/test_gpu_qkernel_pins.py
+// holds the copies to the same bits with the grid-stride forms on and off.
+//
+// Q4_K / Q5_K sub-block s (compile-time after unrolling): A = 2^-24 sum_k x_k q_k on the subnormal
+// codes, then acc = fma(-m1, X_s, fma(2^24 d1, A, acc)); xs = kq_xsum(xf), shared by the weight tiles
+__device__ __forceinline__ f32x4 kq_xsum(f16x8 xf) {
+  // X_s = the sub-block's sum of each row's x: one more MFMA against ones (no separate pass over
+  // X, no barrier)
   typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-  const uint4 v = r.q[s >> 1];
-  const uint32_t w0 = ((s & 1) ? v.z : v.x) ^ 0x80808080u, w1 = ((s & 1) ? v.w : v.y) ^ 0x80808080u;
-  const h2 bias = {(_Float16)1152.0f, (_Float16)1152.0f};
-  auto cv = [&](uint32_t w, uint32_t sel) {
-    const h2 u = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, w, sel));
-    return __builtin_bit_cast(uint32_t, u - bias);
-  };
-  const u4v pk = {cv(w0, 0x04010400u), cv(w0, 0x04030402u), cv(w1, 0x04010400u), cv(w1, 0x04030402u)};
-  return __builtin_bit_cast(f16x8, pk);
+  const f16x8 ones = __builtin_bit_cast(f16x8, u4v{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u});
+  return mfma16(xf, ones, f32x4{0.f, 0.f, 0.f, 0.f});
+}
+__device__ __forceinline__ f32x4 kq_mac(f32x4 acc, uint4 h, uint4 q0, uint4 q1, int s, f16x8 xf, f32x4 xs) {
+  float d1, m1;
+  kq_scale_min(h, s, d1, m1);
+  const float d1s = d1 * 16777216.0f;  // d1 * 2^24 (exact)
+  uint32_t lo, hi;
+  kq_codes(q0, q1, s, lo, hi);
+  const f32x4 A = mfma16(xf, subnormal_frag(lo, hi), f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+  for (int i = 0; i < 4; ++i) acc[i] = __fmaf_rn(-m1, xs[i], __fmaf_rn(d1s, A[i], acc[i]));
+  return acc;
 }
 
-// One block per 16*NT rows, waves split the K/256 super-blocks (SBW per wave).  Lane
-// group g = lane>>4 owns 64 weights of each super-block:
-//   Q4_K: chunk g (qs bytes 32g..32g+31): low nibbles = weights 64g..64g+31 (sub-block
-//         2g), high nibbles = 64g+32.. (sub-block 2g+1);
-//   Q6_K: half h = g>>1, positions l in [16p, 16p+16), p = g&1, each giving the four
-//         weights h*128 + {0,32,64,96} + l.
-//   Q8_0: weights 32s + 8g .. +7 of each of the unit's 8 blocks s (Q4_K's order).
+// X by LDS DMA has landed once at most the N weight loads issued after it are pending (vmcnt
+// retires in issue order); no fence at the barrier: a fence would wait for the weight loads too
+template <int N>
+__device__ __forceinline__ void x_landed() {
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(vmcnt_imm(N));
+  __builtin_amdgcn_s_barrier();
+}
+
+// One block per 16*NT rows, waves split the K/256 super-blocks (SBW per wave).  Lane group
+// g = lane>>4 owns 64 weights of each super-block (qblock.h): k = 32s + 8g .. +7 of every sub-block s
+// (Q4_K, Q5_K, Q8_0), or half hh = g>>1, positions [16p, 16p+16), p = g&1 (Q6_K).
 // MFMA t of a super-block takes 8 of those weights per lane and the X elements of the
 // same k -- a k permutation applied to both operands, so every dot product is unchanged.
 // XM: the X source (gemv_common.h kXGlobal / kXLds / kXRegs, as in k_gemv.hip)
@@ -341,9 +249,10 @@ __device__ __forceinline__ f16x8 q8_frag(const Q8Regs& r, int s) {  // s compile
 // (its own instantiations: as a third run-time branch it raised the registers and the scratch of
 // every K-quant instantiation, the kernel's allocation being the largest branch's), MS_QT_Q5_K = a
 // K-quant matrix with a Q5_K region (regions Q4_K / Q5_K / Q6_K at run time; own instantiations for
-// the same reason).  There the Q4_K body serves both 4- and 5-bit regions: a fourth load per block
-// fetches lane group g's qh bytes -- for a Q4_K region the header's first bytes, masked to zero -- so
-// the load count, and with it the counted X wait, does not depend on the region's type
+// the same reason; matrices without one keep the QF = 0 instantiations).  There the Q4_K body
+// serves both 4- and 5-bit regions: a fourth load per block fetches lane group g's qh bytes -- for
+// a Q4_K region the header's first bytes, masked to zero -- so the load count, and with it the
+// counted X wait, does not depend on the region's type
 template <int QF, int MT, int NT, int EPI, int SBW, int XM, bool RS>
 __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X, QMat qm,
                                                      void* __restrict__ out, int M, int N, int K,
@@ -400,8 +309,17 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
           xr[j][t][m] = as_f16x8(ldg16(X + (size_t)min(m * 16 + fr, M - 1) * ldx + k));
         }
   }
+  // m-tile m's X fragment for MFMA t of this wave's super-block j (its 8 elements from k)
+  auto xfrag = [&](int j, int t, int m, int k) -> f16x8 {
+    const int xrow = min(m * 16 + fr, M - 1);
+    return XR ? xr[XR ? j : 0][XR ? t : 0][XR ? m : 0]
+           : XL ? *(const f16x8*)(smem + x_lds(xrow, k, K))
+                : *(const f16x8*)(X + (size_t)xrow * ldx + k);
+  };
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (QF == MS_QT_Q8_0) {  // packed 272-B units: 8 scales, 4 x 64 B of regrouped quants
+  if constexpr (QF == MS_QT_Q8_0) {
+    // (the multiply-accumulate inline: through a shared function <Q8_0,2,2,SWIGLU,2,kXLds,false> went
+    // from 460 to 488 B of scratch and <Q8_0,3,2,SWIGLU,2,kXLds,true> from 736 to 780 B)
     Q8Regs w[SBW][NT];
 #pragma unroll
     for (int j = 0; j < SBW; ++j)
@@ -437,6 +355,11 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
         }
       }
   } else if (type == MS_QT_Q4_K || (QF == MS_QT_Q5_K && type == MS_QT_Q5_K)) {
+    // kq_mac's arithmetic, statement for statement, but written out on loose arrays: with any shared
+    // function in this loop body (kq_mac, or only kq_scale_min or kq_codes / subnormal_frag; by
+    // reference, by value, as a struct image) the SwiGLU instantiations <0, 1, 2, SWIGLU, 2, kXLds, *>
+    // went from 352 to 548-600 B of scratch (profiles/qblock/README.md).  tests/test_gpu_qkernel_pins.py
+    // holds the two statements of it to the same bits (grid-stride on and off).
     constexpr bool Q5F = QF == MS_QT_Q5_K;
     const bool q5 = Q5F && type == MS_QT_Q5_K;  // block-uniform
     const int bbytes = q5 ? kQ5KBytes : kQ4KBytes;
@@ -447,16 +370,12 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
         const uint8_t* bp = base + (size_t)(rbase + n * 16 + frw) * row_bytes + (size_t)(sbk + sb0 + j) * bbytes;
-        hq[j][n] = ldw16(bp);
-        q0[j][n] = ldw16(bp + 16 + 16 * g);  // sub-blocks 0-3 (quant_rows_kernel's layout)
-        q1[j][n] = ldw16(bp + 80 + 16 * g);  // sub-blocks 4-7
-        if constexpr (Q5F) q5h[j][n] = *(const uint2*)(bp + (q5 ? 144 + 8 * g : 0));
+        hq[j][n] = ldw16(bp + kKqHdr);
+        q0[j][n] = ldw16(bp + kKqNib0 + 16 * g);  // sub-blocks 0-3
+        q1[j][n] = ldw16(bp + kKqNib1 + 16 * g);  // sub-blocks 4-7
+        if constexpr (Q5F) q5h[j][n] = *(const uint2*)(bp + (q5 ? kQ5Qh + 8 * g : 0));
       }
-    if constexpr (XL) {  // the X image has landed once at most the weight loads are pending
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm((Q5F ? 4 : 3) * SBW * NT));
-      __builtin_amdgcn_s_barrier();  // no fence: a fence would wait for the weight loads too
-    }
+    if constexpr (XL) x_landed<(Q5F ? 4 : 3) * SBW * NT>();
     typedef uint32_t u4v __attribute__((ext_vector_type(4)));
     const f16x8 ones = __builtin_bit_cast(f16x8, u4v{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u});
 #pragma unroll
@@ -467,10 +386,7 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
         const int sh = 8 * (s_ & 3);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-          const int xrow = min(m * 16 + fr, M - 1);
-          const f16x8 xf = XR ? xr[XR ? j : 0][XR ? s_ : 0][XR ? m : 0]
-                          : XL ? *(const f16x8*)(smem + x_lds(xrow, k, K))
-                               : *(const f16x8*)(X + (size_t)xrow * ldx + k);
+          const f16x8 xf = xfrag(j, s_, m, k);
           // X_s = the sub-block's sum of each row's x: one more MFMA against ones, shared by
           // the NT weight tiles (no separate pass over X, no barrier)
           const f32x4 xs = mfma16(xf, ones, f32x4{0.f, 0.f, 0.f, 0.f});
@@ -504,6 +420,11 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
       }
   } else {  // Q6_K, packed 224-B blocks
     const int hh = g >> 1, p = g & 1;
+    // one instantiation picks its scale byte by q6_frag's 64-bit form: with the 32-bit select, which every
+    // other kernel keeps (it took 48 B of scratch off the SBW = 2 ones), <0,2,2,SWIGLU,1,kXLds,false>
+    // spilled 424 B for the parent's 416; the 64-bit form everywhere cost nine kernels a wave
+    // (profiles/qblock/README.md).  Same byte, same bits.
+    constexpr bool kSel64 = QF == 0 && MT == 2 && NT == 2 && SBW == 1 && XL && !RS;
     uint4 qa[SBW][NT], qb[SBW][NT], qh[SBW][NT], sc[SBW][NT];
     uint32_t dw[SBW][NT];
 #pragma unroll
@@ -511,17 +432,13 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
         const uint8_t* bp = base + (size_t)(rbase + n * 16 + frw) * row_bytes + (size_t)(sbk + sb0 + j) * kQ6KPacked;
-        qa[j][n] = ldw16(bp + 16 * g);  // raw ql hh*64 + 16p .. (quant_rows_kernel's regrouping)
-        qb[j][n] = ldw16(bp + 64 + 16 * g);  // raw ql hh*64 + 32 + 16p ..
-        qh[j][n] = ldw16(bp + 128 + hh * 32 + 16 * p);
-        sc[j][n] = ldw16(bp + 192);
-        dw[j][n] = *(const uint32_t*)(bp + 208);
+        qa[j][n] = ldw16(bp + kQ6Ql0 + 16 * g);
+        qb[j][n] = ldw16(bp + kQ6Ql1 + 16 * g);
+        qh[j][n] = ldw16(bp + kQ6Qh + hh * 32 + 16 * p);
+        sc[j][n] = ldw16(bp + kQ6Sc);
+        dw[j][n] = *(const uint32_t*)(bp + kQ6D);
       }
-    if constexpr (XL) {  // the X image has landed once at most the weight loads are pending
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm(5 * SBW * NT));
-      __builtin_amdgcn_s_barrier();  // no fence: a fence would wait for the weight loads too
-    }
+    if constexpr (XL) x_landed<5 * SBW * NT>();
 #pragma unroll
     for (int j = 0; j < SBW; ++j)
 #pragma unroll
@@ -530,179 +447,130 @@ __global__ __launch_bounds__(1024) void qgemv_kernel(const f16_t* __restrict__ X
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
           const int k4 = t >> 1, sub = t & 1;
-          const int si = hh * 8 + p + 2 * k4;
-          const float ds = __fmul_rn(d, (float)(int)(int8_t)byte_of(sc[j][n], si));
-          const float nds = -32.0f * ds;  // exact (a power-of-two multiple of an fp16 x int8 product)
-          // the 6-bit codes of 4 weights assembled as bytes of one word (nibble | 2 high bits
-          // << 4), each byte converted straight to fp32 (v_cvt_f32_ubyte*), then
-          // fma(ds, q, -32 ds) = ds * (q - 32) with the single rounding of ggml's product (only
-          // the sign of an exact zero can differ); ~3 VALU per weight instead of ~7
-          const uint4 qsrc = (k4 & 1) ? qb[j][n] : qa[j][n];
-          uint32_t pk[4];
-#pragma unroll
-          for (int w = 0; w < 2; ++w) {
-            const int wi = 2 * sub + w;  // weights li = 4 wi .. 4 wi + 3
-            const uint32_t aw = wi == 0 ? qsrc.x : wi == 1 ? qsrc.y : wi == 2 ? qsrc.z : qsrc.w;
-            const uint32_t hw = wi == 0 ? qh[j][n].x : wi == 1 ? qh[j][n].y : wi == 2 ? qh[j][n].z : qh[j][n].w;
-            const uint32_t q4 = (((k4 >> 1) ? (aw >> 4) : aw) & 0x0F0F0F0Fu) | (((hw >> (2 * k4)) & 0x03030303u) << 4);
-            typedef float f2 __attribute__((ext_vector_type(2)));
-            const f2 ds2 = {ds, ds}, nds2 = {nds, nds};  // two weights per v_pk_fma_f32
-            const f2 y01 = __builtin_elementwise_fma(ds2, f2{(float)(q4 & 0xFFu), (float)((q4 >> 8) & 0xFFu)}, nds2);
-            const f2 y23 = __builtin_elementwise_fma(ds2, f2{(float)((q4 >> 16) & 0xFFu), (float)(q4 >> 24)}, nds2);
-            pk[2 * w] = pack2h(y01.x, y01.y);
-            pk[2 * w + 1] = pack2h(y23.x, y23.y);
-          }
-          const f16x8 wf = __builtin_bit_cast(f16x8, pk);
+          const f16x8 wf = q6_frag<kSel64>(qa[j][n], qb[j][n], qh[j][n], sc[j][n], d, t, hh, p);
           const int k = (sb0 + j) * 256 + hh * 128 + k4 * 32 + 16 * p + 8 * sub;
 #pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            const int xrow = min(m * 16 + fr, M - 1);
-            const f16x8 xf = XR ? xr[XR ? j : 0][XR ? t : 0][XR ? m : 0]
-                            : XL ? *(const f16x8*)(smem + x_lds(xrow, k, K))
-                                 : *(const f16x8*)(X + (size_t)xrow * ldx + k);
-            acc[m][n] = mfma16(xf, wf, acc[m][n]);
-          }
+          for (int m = 0; m < MT; ++m) acc[m][n] = mfma16(xfrag(j, t, m, k), wf, acc[m][n]);
         }
       }
   }
   gemv_finish<MT, NT, EPI, RS>(acc, smem, rinv_off, M, N, ldo, out, n0, ga, pre, rsd);
 }
 
-// ---- the Q6_K lm_head (greedy argmax partials) as a grid-stride two-stage loop.  One-tile
-// blocks (qgemv_kernel) each DMA the whole X image (M x K fp16: 48 KiB at M = 8 -- 385 MB over
-// the vocabulary's 8016 tiles, more than the weights' 323 MB) and pay one exposed weight
-// latency per tile.  Here 2 x 256 resident blocks stage X and the rows' norm factors once,
-// then walk tiles b, b + G, ...: each wave issues the NEXT tile's weight loads (17 VGPRs)
-// before it dequantises and multiplies the current one, and the per-tile cross-wave reduction
-// uses LDS-only barriers so those loads stay in flight.  Per tile the arithmetic is
-// qgemv_kernel<1, 1, ARGMAX, 1, LDS, true>'s exactly (same K split over waves, same MFMA order,
-// same reduction order and epilogue): bit-identical partials.
-struct Q6Regs {
-  uint4 qa, qb, qh, sc;
-  uint32_t dw;
-};
-__device__ __forceinline__ void q6_fetch(Q6Regs& r, const uint8_t* base, int row_bytes, int n0, int fr, int sb,
-                                         int hh, int p) {
-  const uint8_t* bp = base + (size_t)(n0 + fr) * row_bytes + (size_t)sb * kQ6KPacked;
-  r.qa = ldw16(bp + 32 * hh + 16 * p);  // = 16 g: quant_rows_kernel's ql regrouping
-  r.qb = ldw16(bp + 64 + 32 * hh + 16 * p);
-  r.qh = ldw16(bp + 128 + hh * 32 + 16 * p);
-  r.sc = ldw16(bp + 192);
-  r.dw = *(const uint32_t*)(bp + 208);
+// ---- grid-stride forms.  One-tile blocks (qgemv_kernel) each stage the whole X and pay one exposed
+// weight latency per tile; here resident blocks stage X and the rows' norm factors once, then walk
+// tiles b, b + G, ... with the next tile's weight loads in flight under the current tile's
+// multiply, and the per-tile cross-wave reduction uses LDS-only barriers so those loads stay in
+// flight.  Wave w owns super-block w (SBW = 1), MT = 1.
+//
+// once the first tile's LOADS weight loads are issued: X and the statistics (issued first) landed
+template <int LOADS>
+__device__ __forceinline__ void gs_staged(char* smem, int rinv_off, const GemvArgs& ga, int M, bool rs_on) {
+  x_landed<LOADS>();
+  if (rs_on) rs_finish<false>(smem, rinv_off, ga.rs, M, 0.f);
+  lds_sync();
 }
+// the argmax kernels' first steps: row statistics and X once per block, ahead of the first tile's weights
+__device__ __forceinline__ bool gs_argmax_begin(char* smem, const f16_t* X, int M, int K, int rinv_off,
+                                                const GemvArgs& ga) {
+  const bool rs_on = ga.rs.ssq != nullptr;
+  if (rs_on) rs_begin<false>(smem, rinv_off, ga.rs, M);
+  gemv_dma_x(smem, X, M, K, K);
+  __builtin_amdgcn_sched_barrier(0);
+  return rs_on;
+}
+// tile t's cross-wave reduction and argmax partials (gemv_epilogue's order; LDS-only barriers: the
+// next tile's loads stay in flight)
+__device__ __forceinline__ void gs_argmax_tile(f32x4 acc, float* red, const float* rinv, bool rs_on, int t, int M,
+                                               int N, int ldo, float2* out) {
+  constexpr int ELEMS = 256;  // MT = NT = 1
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  *(f32x4*)&red[wave * ELEMS + lane * 4] = acc;
+  lds_sync();
+  if ((int)threadIdx.x < ELEMS) {
+    const int e = threadIdx.x, l = (e >> 2) & 63, j = e & 3;
+    const int row = 4 * (l >> 4) + j, col = t * 16 + (l & 15);
+    float v = -INFINITY;
+    if (row < M && col < N) {
+      float sum = 0.f;
+      for (int q = 0; q < nw; ++q) sum += red[q * ELEMS + e];
+      v = sum * (rs_on ? rinv[row] : 1.0f);
+    }
+    if (!(v == v)) v = -INFINITY;
+    int idx = col;
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) amax_merge_dev(v, idx, __shfl_xor(v, o, 64), __shfl_xor(idx, o, 64));
+    // (a 32-bit offset from the scalar base: a 64-bit lane address held across the loop spilled)
+    if ((l & 15) == 0 && row < M)
+      *(float2*)((char*)out + (uint32_t)(row * ldo + t) * 8u) = make_float2(v, __int_as_float(idx));
+  }
+  lds_sync();  // red is rewritten by the next tile
+}
+
+// ---- the Q6_K lm_head (greedy argmax partials).  One-tile blocks each DMA the whole X image
+// (M x K fp16: 48 KiB at M = 8 -- 385 MB over the vocabulary's 8016 tiles, more than the weights'
+// 323 MB); here 2 x 256 resident blocks stage it once, and each wave issues the NEXT tile's weight
+// loads (17 VGPRs) before it dequantises and multiplies the current one.  Per tile the arithmetic is
+// qgemv_kernel<0, 1, 1, ARGMAX, 1, LDS, false>'s (same K split over waves, same MFMA order, same
+// reduction order and epilogue): bit-identical partials.  launch_qgemv clears the row scale for the
+// argmax (a row's positive scale never moves its argmax), as qgemv_go does for the one-tile kernels:
+// rs_on is false in every launch today, and the rinv path is kept for a caller that wants scaled maxima.
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(6, 8))) void qgemv_q6_argmax_gs_kernel(const f16_t* __restrict__ X, QMat qm,
                                                                 float2* __restrict__ out, int M, int N, int K,
                                                                 int ldo, int red_off, int rinv_off, GemvArgs ga) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int ELEMS = 256;  // MT = NT = 1
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 15, g = lane >> 4, hh = g >> 1, p = g & 1;
   const int tiles = N / 16, G = gridDim.x;
   const uint8_t* base = qm.base0;
   const int row_bytes = qm.row_bytes0;
-  // 0. row statistics and X once per block, then the first tile's weights
-  const bool rs_on = ga.rs.ssq != nullptr;
-  if (rs_on) rs_begin<false>(smem, rinv_off, ga.rs, M);
-  gemv_dma_x(smem, X, M, K, K);
-  __builtin_amdgcn_sched_barrier(0);
+  // this lane's block of tile t: row 16 t + fr, super-block `wave`
+  auto block = [&](int t) { return base + (size_t)(t * 16 + fr) * row_bytes + (size_t)wave * kQ6KPacked; };
+  const bool rs_on = gs_argmax_begin(smem, X, M, K, rinv_off, ga);
   Q6Regs cur, nxt;
   int t = blockIdx.x;
-  q6_fetch(cur, base, row_bytes, t * 16, fr, wave, hh, p);
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_waitcnt(vmcnt_imm(5));  // X and the statistics landed (issued first)
-  __builtin_amdgcn_s_barrier();
-  float* rinv = (float*)(smem + rinv_off);
-  if (rs_on) rs_finish<false>(smem, rinv_off, ga.rs, M, 0.f);
-  lds_sync();
+  q6_fetch(cur, block(t), g);
+  gs_staged<5>(smem, rinv_off, ga, M, rs_on);
+  const float* rinv = (const float*)(smem + rinv_off);
   float* red = (float*)(smem + red_off);
   for (; t < tiles; t += G) {
     const bool more = t + G < tiles;
-    if (more) q6_fetch(nxt, base, row_bytes, (t + G) * 16, fr, wave, hh, p);
+    if (more) q6_fetch(nxt, block(t + G), g);
     __builtin_amdgcn_sched_barrier(0);
     if (more) __builtin_amdgcn_s_waitcnt(vmcnt_imm(5));
     else __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
-    // qgemv_kernel's Q6_K body, SBW = 1 (this wave's super-block = its index), MT = NT = 1
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     const float d = h2f_lo(cur.dw);
 #pragma unroll
     for (int tt = 0; tt < 8; ++tt) {
-      const int k4 = tt >> 1, sub = tt & 1;
-      const int si = hh * 8 + p + 2 * k4;
-      const float ds = __fmul_rn(d, (float)(int)(int8_t)byte_of(cur.sc, si));
-      const float nds = -32.0f * ds;
-      const uint4 qsrc = (k4 & 1) ? cur.qb : cur.qa;
-      uint32_t pk[4];
-#pragma unroll
-      for (int w = 0; w < 2; ++w) {
-        const int wi = 2 * sub + w;
-        const uint32_t aw = wi == 0 ? qsrc.x : wi == 1 ? qsrc.y : wi == 2 ? qsrc.z : qsrc.w;
-        const uint32_t hw = wi == 0 ? cur.qh.x : wi == 1 ? cur.qh.y : wi == 2 ? cur.qh.z : cur.qh.w;
-        const uint32_t q4 = (((k4 >> 1) ? (aw >> 4) : aw) & 0x0F0F0F0Fu) | (((hw >> (2 * k4)) & 0x03030303u) << 4);
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        const f2 ds2 = {ds, ds}, nds2 = {nds, nds};
-        const f2 y01 = __builtin_elementwise_fma(ds2, f2{(float)(q4 & 0xFFu), (float)((q4 >> 8) & 0xFFu)}, nds2);
-        const f2 y23 = __builtin_elementwise_fma(ds2, f2{(float)((q4 >> 16) & 0xFFu), (float)(q4 >> 24)}, nds2);
-        pk[2 * w] = pack2h(y01.x, y01.y);
-        pk[2 * w + 1] = pack2h(y23.x, y23.y);
-      }
-      const f16x8 wf = __builtin_bit_cast(f16x8, pk);
-      const int k = wave * 256 + hh * 128 + k4 * 32 + 16 * p + 8 * sub;
-      const int xrow = min(fr, M - 1);
-      acc = mfma16(*(const f16x8*)(smem + x_lds(xrow, k, K)), wf, acc);
+      const int k = wave * 256 + hh * 128 + (tt >> 1) * 32 + 16 * p + 8 * (tt & 1);
+      acc = mfma16(*(const f16x8*)(smem + x_lds(min(fr, M - 1), k, K)), q6_frag(cur, d, tt, hh, p), acc);
     }
-    // cross-wave reduction (LDS-only barriers: the next tile's loads stay in flight)
-    *(f32x4*)&red[wave * ELEMS + lane * 4] = acc;
-    lds_sync();
-    if ((int)threadIdx.x < ELEMS) {
-      const int e = threadIdx.x, l = (e >> 2) & 63, j = e & 3;
-      const int row = 4 * (l >> 4) + j, col = t * 16 + (l & 15);
-      float v = -INFINITY;
-      if (row < M && col < N) {
-        float sum = 0.f;
-        for (int q = 0; q < nw; ++q) sum += red[q * ELEMS + e];
-        v = sum * (rs_on ? rinv[row] : 1.0f);
-      }
-      if (!(v == v)) v = -INFINITY;
-      int idx = col;
-#pragma unroll
-      for (int o = 4; o < 64; o <<= 1) amax_merge_dev(v, idx, __shfl_xor(v, o, 64), __shfl_xor(idx, o, 64));
-      if ((l & 15) == 0 && row < M) out[(size_t)row * ldo + t] = make_float2(v, __int_as_float(idx));
-    }
-    lds_sync();  // red is rewritten by the next tile
+    gs_argmax_tile(acc, red, rinv, rs_on, t, M, N, ldo, out);
     cur = nxt;
   }
 }
 
-// ---- the Q8_0 lm_head (418 MB, the largest stream of a Q8_0 step) in the same form: resident
-// blocks stage X and the norm factors once and walk tiles b, b + G, ... with the next tile's 5
-// loads in flight under the current tile's 8 MFMAs -- issued in two halves, the second once
+// ---- the Q8_0 lm_head (418 MB, the largest stream of a Q8_0 step) in the same form, the next
+// tile's 5 loads in flight under the current tile's 8 MFMAs -- issued in two halves, the second once
 // blocks 0-3 are multiplied and their 8 VGPRs free (both tiles whole, 40 VGPRs, spilled under
 // the 80-VGPR cap of two resident 12-wave blocks per CU).  Per tile the arithmetic is
-// qgemv_kernel<Q8_0, 1, 1, ARGMAX, 1, LDS, false>'s exactly: bit-identical partials.
+// qgemv_kernel<Q8_0, 1, 1, ARGMAX, 1, LDS, false>'s: bit-identical partials.
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(6, 8))) void qgemv_q8_argmax_gs_kernel(const f16_t* __restrict__ X, QMat qm,
                                                                 float2* __restrict__ out, int M, int N, int K,
                                                                 int ldo, int red_off, int rinv_off, GemvArgs ga) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int ELEMS = 256;  // MT = NT = 1
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 15, g = lane >> 4;
   const int tiles = N / 16, G = gridDim.x;
   const uint8_t* base = qm.base0;
   const int row_bytes = qm.row_bytes0;
-  // 0. row statistics and X once per block, then the first tile's weights
-  const bool rs_on = ga.rs.ssq != nullptr;
-  if (rs_on) rs_begin<false>(smem, rinv_off, ga.rs, M);
-  gemv_dma_x(smem, X, M, K, K);
-  __builtin_amdgcn_sched_barrier(0);
+  const bool rs_on = gs_argmax_begin(smem, X, M, K, rinv_off, ga);
   Q8Regs cur, nxt;
   int t = blockIdx.x;
   q8_fetch(cur, base + (size_t)t * 16 * row_bytes, row_bytes, fr, wave, g);
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_waitcnt(vmcnt_imm(5));  // X and the statistics landed (issued first)
-  __builtin_amdgcn_s_barrier();
-  float* rinv = (float*)(smem + rinv_off);
-  if (rs_on) rs_finish<false>(smem, rinv_off, ga.rs, M, 0.f);
-  lds_sync();
+  gs_staged<5>(smem, rinv_off, ga, M, rs_on);
+  const float* rinv = (const float*)(smem + rinv_off);
   float* red = (float*)(smem + red_off);
   // this lane's X fragment of block s_: chunk (wave * 32 + 4 s_ + g) ^ (row & 7) of its row; the
   // swizzle touches chunk bits 0-2 only, so block s_ sits 128 (s_ >> 1) bytes behind block s_ & 1
@@ -715,8 +583,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     const uint32_t ntile = (uint32_t)(t + G) * 16u * (uint32_t)row_bytes;
     if (more) q8_fetch_half<0>(nxt, base, ntile, row_bytes, fr, wave, g);
     __builtin_amdgcn_sched_barrier(0);
-    // qgemv_kernel's Q8_0 body, SBW = 1 (this wave's unit = its index), MT = NT = 1; the waits
-    // for `cur` are the compiler's own (register dependencies: no DMA is in flight here)
+    // the waits for `cur` are the compiler's own (register dependencies: no DMA is in flight here)
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s_ = 0; s_ < 8; ++s_) {
@@ -732,46 +599,17 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
       // two blocks' products in flight at most: all eight cost 32 VGPRs and spilled the prefetch
       if (s_ & 1) __builtin_amdgcn_sched_barrier(0);
     }
-    // cross-wave reduction (LDS-only barriers: the next tile's loads stay in flight)
-    *(f32x4*)&red[wave * ELEMS + lane * 4] = acc;
-    lds_sync();
-    if ((int)threadIdx.x < ELEMS) {
-      const int e = threadIdx.x, l = (e >> 2) & 63, j = e & 3;
-      const int row = 4 * (l >> 4) + j, col = t * 16 + (l & 15);
-      float v = -INFINITY;
-      if (row < M && col < N) {
-        float sum = 0.f;
-        for (int q = 0; q < nw; ++q) sum += red[q * ELEMS + e];
-        v = sum * (rs_on ? rinv[row] : 1.0f);
-      }
-      if (!(v == v)) v = -INFINITY;
-      int idx = col;
-#pragma unroll
-      for (int o = 4; o < 64; o <<= 1) amax_merge_dev(v, idx, __shfl_xor(v, o, 64), __shfl_xor(idx, o, 64));
-      // (a 32-bit offset from the scalar base: a 64-bit lane address held across the loop spilled)
-      if ((l & 15) == 0 && row < M)
-        *(float2*)((char*)out + (uint32_t)(row * ldo + t) * 8u) = make_float2(v, __int_as_float(idx));
-    }
-    lds_sync();  // red is rewritten by the next tile
+    gs_argmax_tile(acc, red, rinv, rs_on, t, M, N, ldo, out);
     cur = nxt;
   }
 }
 
-// ---- the Q4_K gate/up projection (SwiGLU epilogue) in the same grid-stride form: 256 blocks
-// of 12 waves (wave w = super-block w of the 3072-long rows) take X into registers ONCE (the
-// one-tile kernel's 512 blocks each re-read the 8 x 3072 X -- 49 MB of L2 traffic against
-// 28 MB of weights), then walk 32-row tiles (16 gate + 16 up rows) with the next tile's 6
-// weight loads per lane in flight under the current tile's dequant.  Per tile the arithmetic
-// is qgemv_kernel<1, 2, SWIGLU, 1, REGS, RS>'s exactly: bit-identical outputs.
-struct Q4Regs {
-  uint4 hq, q0, q1;
-};
-__device__ __forceinline__ void q4_fetch(Q4Regs& r, const uint8_t* base, int row_bytes, int row, int sb, int g) {
-  const uint8_t* bp = base + (size_t)row * row_bytes + (size_t)sb * kQ4KBytes;
-  r.hq = ldw16(bp);
-  r.q0 = ldw16(bp + 16 + 16 * g);
-  r.q1 = ldw16(bp + 80 + 16 * g);
-}
+// ---- the Q4_K gate/up projection (SwiGLU epilogue): 256 blocks of 12 waves (wave w = super-block
+// w of the 3072-long rows) take X into registers ONCE (the one-tile kernel's 512 blocks each re-read
+// the 8 x 3072 X -- 49 MB of L2 traffic against 28 MB of weights), then walk 32-row tiles (16 gate
+// + 16 up rows) with the next tile's 6 weight loads per lane in flight under the current tile's
+// dequant.  Per tile the arithmetic is qgemv_kernel<0, 1, 2, SWIGLU, 1, REGS, RS>'s: bit-identical
+// outputs.
 __global__ __launch_bounds__(768) void qgemv_q4_swiglu_gs_kernel(const f16_t* __restrict__ X, QMat qm,
                                                                  f16_t* __restrict__ out, int M, int N, int K,
                                                                  int ldo, int rinv_off, GemvArgs ga) {
@@ -790,25 +628,21 @@ __global__ __launch_bounds__(768) void qgemv_q4_swiglu_gs_kernel(const f16_t* __
 #pragma unroll
   for (int t = 0; t < 8; ++t) xr[t] = as_f16x8(ldg16(xrow + (wave * 8 + t) * 32 + 8 * g));
   __builtin_amdgcn_sched_barrier(0);
-  Q4Regs cur[NT], nxt[NT];
-  int t = blockIdx.x;
+  // tile t's weight tile n: this lane's row 32 t - row0 + 16 n + fr, super-block `wave`
+  auto fetch = [&](KqRegs (&r)[NT], int t) {
 #pragma unroll
-  for (int n = 0; n < NT; ++n) q4_fetch(cur[n], base, row_bytes, t * 32 - row0 + n * 16 + fr, wave, g);
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_waitcnt(vmcnt_imm(3 * NT));  // X and the statistics landed (issued first)
-  __builtin_amdgcn_s_barrier();
+    for (int n = 0; n < NT; ++n)
+      kq_fetch(r[n], base + (size_t)(t * 32 - row0 + n * 16 + fr) * row_bytes + (size_t)wave * kQ4KBytes, g);
+  };
+  KqRegs cur[NT], nxt[NT];
+  int t = blockIdx.x;
+  fetch(cur, t);
+  gs_staged<3 * NT>(smem, rinv_off, ga, M, rs_on);
   const float* rinv = (const float*)(smem + rinv_off);
-  if (rs_on) rs_finish<false>(smem, rinv_off, ga.rs, M, 0.f);
-  lds_sync();
   float* red = (float*)smem;
-  typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-  const f16x8 ones = __builtin_bit_cast(f16x8, u4v{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u});
   for (; t < tiles; t += G) {
     const bool more = t + G < tiles;
-    if (more) {
-#pragma unroll
-      for (int n = 0; n < NT; ++n) q4_fetch(nxt[n], base, row_bytes, (t + G) * 32 - row0 + n * 16 + fr, wave, g);
-    }
+    if (more) fetch(nxt, t + G);
     __builtin_amdgcn_sched_barrier(0);
     if (more) __builtin_amdgcn_s_waitcnt(vmcnt_imm(3 * NT));
     else __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
@@ -817,27 +651,9 @@ __global__ __launch_bounds__(768) void qgemv_q4_swiglu_gs_kernel(const f16_t* __
     for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s_ = 0; s_ < 8; ++s_) {
-      const int sh = 8 * (s_ & 3);
-      const f16x8 xf = xr[s_];
-      const f32x4 xs = mfma16(xf, ones, f32x4{0.f, 0.f, 0.f, 0.f});
+      const f32x4 xs = kq_xsum(xr[s_]);
 #pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        const uint4 h = cur[n].hq;
-        const uint32_t scw = s_ < 4 ? (h.y & 0x3F3F3F3Fu) : ((h.w & 0x0F0F0F0Fu) | ((h.y >> 2) & 0x30303030u));
-        const uint32_t mw = s_ < 4 ? (h.z & 0x3F3F3F3Fu) : (((h.w >> 4) & 0x0F0F0F0Fu) | ((h.z >> 2) & 0x30303030u));
-        const float d1 = __fmul_rn(h2f_lo(h.x), (float)((scw >> sh) & 0xFFu));
-        const float m1 = __fmul_rn(h2f_lo(h.x >> 16), (float)((mw >> sh) & 0xFFu));
-        const float d1s = d1 * 16777216.0f;
-        const uint4 qq = s_ < 4 ? cur[n].q0 : cur[n].q1;
-        const int si = s_ & 3;
-        const uint32_t qw = si == 0 ? qq.x : si == 1 ? qq.y : si == 2 ? qq.z : qq.w;
-        const uint32_t lo = qw & 0x0F0F0F0Fu, hi = (qw >> 4) & 0x0F0F0F0Fu;
-        const u4v pk = {__builtin_amdgcn_perm(0u, lo, 0x0C010C00u), __builtin_amdgcn_perm(0u, lo, 0x0C030C02u),
-                        __builtin_amdgcn_perm(0u, hi, 0x0C010C00u), __builtin_amdgcn_perm(0u, hi, 0x0C030C02u)};
-        const f32x4 A = mfma16(xf, __builtin_bit_cast(f16x8, pk), f32x4{0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[n][i] = __fmaf_rn(-m1, xs[i], __fmaf_rn(d1s, A[i], acc[n][i]));
-      }
+      for (int n = 0; n < NT; ++n) acc[n] = kq_mac(acc[n], cur[n].h, cur[n].q0, cur[n].q1, s_, xr[s_], xs);
     }
     // cross-wave reduction and the SwiGLU epilogue (gemv_epilogue's order), LDS-only barriers
 #pragma unroll
