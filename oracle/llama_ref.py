@@ -169,7 +169,9 @@ class OracleLlama:
         of optional callables: ``"new_kv"(layer, k, v) -> (k, v)`` replaces the new tokens' RoPE
         (k [T, Hk, D] arrives rounded but un-roped; what it returns is cached and attended), and
         ``"attend"(layer, k, v) -> (k, v)`` edits the [S, Hk, D] keys and values this call attends
-        to without touching the cache (one new token only: the causal mask is not re-derived)."""
+        to without touching the cache (one new token only: the causal mask is not re-derived), and
+        ``"mask"(layer, mask) -> mask`` edits the [T, S] boolean causal mask (True = hidden) before
+        it is applied (tests/attn_keys_ref.py; every row must keep one visible key)."""
         cfg, w = self.cfg, self.w
         ids = np.asarray(ids, dtype=np.int64)
         T = ids.shape[0]
@@ -228,6 +230,8 @@ class OracleLlama:
             vq = np.repeat(v, G, axis=1)
             s = mm(q.transpose(1, 0, 2), kq.transpose(1, 2, 0)) * scale  # [Hq, T, S]
             mask = (np.arange(S)[None, :] > (p0 + np.arange(T))[:, None])
+            if "mask" in mut:
+                mask = mut["mask"](l, mask)
             s = np.where(mask[None], np.float32(-np.inf), s)
             s = s - s.max(axis=-1, keepdims=True)
             p = np.exp(s)

@@ -92,11 +92,12 @@ def _engine(case, monkeypatch, env, n_pages=None):
 
 
 class Pools:
-    """Both pools as [layer][slot][page][kv head][64][head_dim] fp16 bit patterns (slot-major pool)."""
+    """Both pools as [layer][slot][page][kv head][64][head_dim] fp16 bit patterns (slot-major pool).
+    ``hk``: the engine's kv heads where it is not TINY (tests/test_gpu_attn_keys.py)."""
 
-    def __init__(self, e, c):
-        self.B, self.max_pages = c["max_batch"], (c["max_ctx"] + PAGE - 1) // PAGE
-        shape = (NL, self.B, self.max_pages, HK, PAGE, D)
+    def __init__(self, e, c, hk=HK):
+        self.B, self.max_pages, self.hk = c["max_batch"], (c["max_ctx"] + PAGE - 1) // PAGE, hk
+        shape = (NL, self.B, self.max_pages, hk, PAGE, D)
         nbytes = int(np.prod(shape)) * 2
         self.k = e.debug_read(L.MS_DBG_KPOOL, 0, nbytes).view(np.uint16).reshape(shape)
         self.v = e.debug_read(L.MS_DBG_VPOOL, 0, nbytes).view(np.uint16).reshape(shape)
@@ -104,7 +105,7 @@ class Pools:
     def rows(self, which, layer, slot, n):
         """[n][kv head][head_dim] fp32: positions 0..n-1 of one slot."""
         p = getattr(self, which)[layer, slot].view(np.float16)
-        return p.transpose(0, 2, 1, 3).reshape(self.max_pages * PAGE, HK, D)[:n].astype(np.float32)
+        return p.transpose(0, 2, 1, 3).reshape(self.max_pages * PAGE, self.hk, D)[:n].astype(np.float32)
 
 
 def _check_stray(before, after, old_lens, new_lens):
