@@ -71,7 +71,9 @@ enum ms_tensor {
   MS_T_WUP = 8,        /* [ffn][hidden]            */
   MS_T_WDOWN = 9,      /* [hidden][ffn]            */
   MS_T_FINAL_NORM = 10,/* [hidden]                 */
-  MS_T_LM_HEAD = 11    /* [vocab][hidden]; only when tie_embeddings == 0 */
+  MS_T_LM_HEAD = 11,   /* [vocab][hidden]; only when tie_embeddings == 0 */
+  MS_T_Q_NORM = 12,    /* [head_dim]; QK-norm engines only (ms_enable_qk_norm) */
+  MS_T_K_NORM = 13     /* [head_dim]; QK-norm engines only */
 };
 
 typedef struct ms_config {
@@ -149,6 +151,14 @@ int ms_create(const ms_config* cfg, ms_engine** out);
 int ms_destroy(ms_engine* e);
 /* e == NULL returns the last error of a failed ms_create / op call */
 const char* ms_last_error(const ms_engine* e);
+
+/* QK-norm models (Qwen3): every layer normalises each Q head and each K head (RMSNorm over the
+   head's 128 values, fp16 gains MS_T_Q_NORM / MS_T_K_NORM shared by the heads) between the QKV
+   projection and RoPE, in prefill and decode alike.  Call after ms_create and before any weight
+   load or request; afterwards it returns MS_EBUSY.  It allocates the gains (1.0 until loaded;
+   ms_init_synthetic* leaves them there) and lists them in ms_weight_regions after every other
+   region.  Such an engine never runs the persistent decode step (ms_set_persist returns 0). */
+int ms_enable_qk_norm(ms_engine* e);
 
 /* ---- weights ---------------------------------------------------------------- */
 int ms_load_weight(ms_engine* e, int32_t tensor, int32_t layer, const uint16_t* host_f16,
@@ -401,6 +411,19 @@ int ms_op_qdgemm(const void* X, int32_t ggml_type, const void* packed_rows, void
    (exact) keeps un-normalised residual rows up to ~1e6 inside fp16 (kernels.h kXgScale). */
 int ms_op_rmsnorm(const void* x, const void* w, void* y, float* ssq, int32_t rows, int32_t hidden,
                   const int32_t* row_idx, void* stream);
+/* The QK-norm kernel (k_qknorm.hip) on device operands.  qkv: fp16 [T][(n_heads + 2 n_kv_heads) * 128]
+   rows with rope-permuted Q / K heads.  slabs == NULL: the rows form, reading qkv.  Else the slabs
+   form: S (1..8) fp32 split-K slabs [S][T][row] folded in slab order, scaled by the row scale set
+   with ms_op_set_row_scale (statistics [tiles][T], tiles <= 256; none set: no scale) and rounded to
+   fp16, which also writes the K / V parts of the qkv rows.  Per Q / K head: RMSNorm with the fp16
+   gains q_gain / k_gain [128] (logical dim order), RoPE with the caller's cos / sin tables
+   [positions][64] at tok_pos[t], one rounding.  Q is written rotated, natural dim order, into its
+   qkv row; K and V go to page block_table[tok_slot[t]][tok_pos[t] / 64], offset tok_pos[t] % 64 of
+   the pools [page][n_kv_heads][64][128].  The caller keeps every position inside its tables. */
+int ms_op_qk_norm_rope(void* qkv, const float* slabs, int32_t S, int32_t T, int32_t n_heads, int32_t n_kv_heads,
+                       const int32_t* tok_pos, const int32_t* tok_slot, const float* cos_tab, const float* sin_tab,
+                       const void* q_gain, const void* k_gain, float eps, void* k_pool, void* v_pool,
+                       const int32_t* block_table, int32_t max_pages, void* stream);
 /* ids[r] = argmax_j logits[r][j] (ties -> lowest j; -1 when no logit of the row is finite) */
 int ms_op_argmax(const void* logits, int32_t rows, int32_t n, int32_t* ids, void* stream);
 /* ids[r] = the lowest id of the largest {max, id} partial of row r (MS_EPI_ARGMAX output) */

@@ -117,6 +117,16 @@ struct DecodeSettings {
   }
 };
 
+// The default splits are tuned for K = 3072 / 8192 (Llama-3.2-3B).  At another width (Qwen3-8B:
+// 4096 / 12288, where 6 does not divide 4096 in 64-k steps) a large-regime default steps down to
+// the largest split whose slabs are whole 64-k steps -- valid, not tuned; the small regime's
+// pick_form already falls back to one slab where a GEMV refuses the split.  One value per engine,
+// so a row's sum order is the same at every row count.  The MS_* overrides are taken as given.
+inline int fit_split(int S, int K) {
+  while (S > 1 && K % (64 * S) != 0) --S;
+  return S;
+}
+
 inline void env_int(const char* name, int& v) { if (const char* s = getenv(name)) v = atoi(s); }
 inline void env_flag(const char* name, bool& v) { if (const char* s = getenv(name)) v = atoi(s) != 0; }
 
@@ -139,6 +149,7 @@ inline DecodeSettings resolve_settings(const ms_config& c) {
     s.dsplit_qkv = 3;
     s.dsplit_down = 4;
   }
+  s.dsplit_qkv = fit_split(s.dsplit_qkv, s.H); s.dsplit_o = fit_split(s.dsplit_o, s.QD); s.dsplit_down = fit_split(s.dsplit_down, s.F);
   env_int("MS_DSPLIT_QKV", s.dsplit_qkv); env_int("MS_DSPLIT_O", s.dsplit_o); env_int("MS_DSPLIT_DOWN", s.dsplit_down);
   if (const char* v = getenv("MS_DWN")) s.dwn_qkv = s.dwn_o = s.dwn_down = s.dwn_lm = atoi(v) == 8 ? 8 : 4;
   for (int* d : {&s.dsplit_qkv, &s.dsplit_o, &s.dsplit_down}) *d = std::min(std::max(*d, 1), kMaxSplit);
@@ -151,6 +162,10 @@ inline DecodeSettings resolve_settings(const ms_config& c) {
   // so every step of it runs the same arithmetic)
   if (!gemv_rs_supported(c.max_batch, s.H / s.resid_rt)) s.resid_fuse = false;
   const int Bg = std::min(c.max_batch, kMaxGemvRows);
+  // ... and the fp16 GEMV takes O and down with that epilogue (not at Qwen3-8B's K = 12288 down:
+  // split-K slabs + residual_rmsnorm there, like the K-quant rule below)
+  if (!gemv_supported(Bg, s.H, s.QD, MS_GEMV_EPI_RESID_SSQ) || !gemv_supported(Bg, s.H, s.F, MS_GEMV_EPI_RESID_SSQ))
+    s.resid_fuse = false;
   s.qresid_ok = qgemv_supported(Bg, s.H, s.QD, MS_GEMV_EPI_RESID_SSQ) &&
                 qgemv_supported(Bg, s.H, s.F, MS_GEMV_EPI_RESID_SSQ) &&
                 qgemv_supported(Bg, 2 * s.F, s.H, MS_GEMV_EPI_SWIGLU, s.H / s.resid_rt);

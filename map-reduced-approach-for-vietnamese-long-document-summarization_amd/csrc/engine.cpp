@@ -84,6 +84,7 @@ struct Seq {
 struct Layer {
   f16_t *attn_norm = nullptr, *wqkv = nullptr, *wo = nullptr, *ffn_norm = nullptr,
          *wgu = nullptr, *wdown = nullptr;
+  f16_t *q_norm = nullptr, *k_norm = nullptr;  // QK-norm engines: the per-head gains [head_dim]
 };
 
 }  // namespace
@@ -94,6 +95,10 @@ struct ms_engine {
   hipStream_t stream = nullptr;
   int H = 0, Hq = 0, Hk = 0, D = 128, F = 0, V = 0, L = 0, QKVN = 0;
   int max_pages = 0, n_pages = 0, Tmax = 0;
+  // QK-norm engines (ms_enable_qk_norm; Qwen3): per-head RMSNorm of Q and K before RoPE.  A switch
+  // per engine, set before the first weight load or request (`started`); every other engine
+  // launches exactly what it did without it.
+  bool qk_norm = false, started = false;
   bool slot_major = false;  // pool of max_batch x max_pages: slot s owns pages [s*max_pages, +max_pages)
   std::vector<void*> allocs;
   std::vector<Layer> layers;
@@ -361,7 +366,9 @@ struct ms_engine {
     // epilogue, one behind residual_rmsnorm
     const int gu_tiles = S.resid_fused(nullptr) ? H / S.resid_rt : 1;
     return residual_rmsnorm_supported(kMaxSplit, H) &&
-           (S.attn_slabs ? gemv_split_supported(Bg, QKVN, H, 1) : gemv_supported(Bg, QKVN, H, MS_GEMV_EPI_ROPE_KV)) &&
+           (S.attn_slabs ? gemv_split_supported(Bg, QKVN, H, 1)
+                         : gemv_supported(Bg, QKVN, H, qk_norm ? MS_GEMV_EPI_STORE_F16 : MS_GEMV_EPI_ROPE_KV,
+                                          qk_norm ? gu_tiles : 0)) &&
            gemv_supported(Bg, 2 * F, H, MS_GEMV_EPI_SWIGLU, gu_tiles) &&
            gemv_split_supported(Bg, H, Hq * D, 1) && gemv_split_supported(Bg, H, F, 1) &&
            (!S.resid_fuse || (gemv_supported(Bg, H, Hq * D, MS_GEMV_EPI_RESID_SSQ) &&
@@ -426,12 +433,36 @@ struct ms_engine {
     }
   }
 
+  // QK-norm engines: norm + RoPE + K/V scatter of T rows (k_qknorm.hip) -- from the fp16 qkv rows,
+  // or from S split-K slabs of the QKV projection with its deferred row scale
+  void qk_norm_rope(int l, int T, const int32_t* tok_pos, const int32_t* tok_slot, const KVView& kv,
+                    const float* slabs_in = nullptr, int S = 0, const RowScale& rs = RowScale{}) {
+    prof_begin(K_MISC);
+    launch_qk_norm_rope(qkv, slabs_in, S, T, rs, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab, layers[l].q_norm,
+                        layers[l].k_norm, cfg.norm_eps, kv, stream);
+    prof_end(K_MISC);
+  }
+
   void run_layer_fused_decode(int l, int B, const int32_t* tok_pos, const int32_t* tok_slot,
                               const DecodeAttnArgs& da) {
     KVView kv = kv_layer(l);
     const RowScale rs_attn = cur_rs;
     DecodeQKV qa{nullptr, slabs, 0, cos_tab, sin_tab, rs_attn};
-    if (S.attn_slabs) {
+    if (qk_norm) {
+      // the GEMV RoPE epilogue and attention's slab prologue cannot see a whole head: the QKV
+      // projection is launched as ever (slabs, or fp16 rows with the row scale where the epilogue
+      // would run), the norm kernel rotates and scatters, and attention reads rows in every regime
+      if (S.attn_slabs) {
+        const int nS = proj_split(mat(QS_QKV, l), xb, B);
+        qk_norm_rope(l, B, tok_pos, tok_slot, kv, slabs, nS, rs_attn);
+      } else {
+        GemvArgs ga{};
+        ga.rs = rs_attn;
+        proj(mat(QS_QKV, l), xb, qkv, B, QKVN, MS_GEMV_EPI_STORE_F16, &ga, K_GEMV, sizeof(f16_t));
+        qk_norm_rope(l, B, tok_pos, tok_slot, kv);
+      }
+      qa = DecodeQKV{qkv, nullptr, 0, cos_tab, sin_tab, RowScale{}};
+    } else if (S.attn_slabs) {
       // QKV -> unscaled slabs; attention adds them, applies the row's deferred-norm factor and
       // RoPE, and writes the new K/V (k_attn.hip): one factor per attention block, not per
       // QKV tile
@@ -472,13 +503,19 @@ struct ms_engine {
     gemm_or_gemv(xb, Ly.wqkv, qkv, T, QKVN, H, QKVN, MS_EPI_STORE_F16, decode, kc, &rs_attn);
     prof_begin(K_MISC);
     // prefill: K / V only -- the attention kernel rotates Q while staging it (pa.cos_tab)
-    launch_rope_kv(qkv, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab, kv, stream, decode || !pa.cos_tab);
+    if (qk_norm)  // Q too: the norm sits between the projection and the rotation
+      launch_qk_norm_rope(qkv, nullptr, 0, 0, RowScale{}, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab, Ly.q_norm,
+                          Ly.k_norm, cfg.norm_eps, kv, stream);
+    else
+      launch_rope_kv(qkv, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab, kv, stream, decode || !pa.cos_tab);
     prof_end(K_MISC);
     if (decode) {
       attn_decode(DecodeQKV{qkv, nullptr, 0, cos_tab, sin_tab, RowScale{}}, kv, da);
     } else {
+      PrefillAttnArgs pq = pa;
+      if (qk_norm) pq.cos_tab = pq.sin_tab = nullptr;  // Q arrives rotated
       prof_begin(K_ATTN_PREFILL);
-      launch_attn_prefill(qkv, attn, Hq, Hk, kv, pa, stream);
+      launch_attn_prefill(qkv, attn, Hq, Hk, kv, pq, stream);
       prof_end(K_ATTN_PREFILL);
     }
     const f16_t* g_next = l + 1 < L ? layers[l + 1].attn_norm : final_norm;
@@ -570,6 +607,11 @@ struct ms_engine {
     qs(lmq);
     for (const auto& l : lq)
       for (const QSlot& q : l) qs(q);
+    if (qk_norm)  // after every region a non-QK-norm engine lists
+      for (const Layer& Ly : layers) {
+        r.push_back({Ly.q_norm, (size_t)D * 2});
+        r.push_back({Ly.k_norm, (size_t)D * 2});
+      }
     return r;
   }
 
@@ -809,6 +851,26 @@ const char* ms_last_error(const ms_engine* e) {
   return g_last_error.c_str();
 }
 
+int ms_enable_qk_norm(ms_engine* e) {
+  if (!e) return MS_EINVAL;
+  return guarded(e, [&]() -> int {
+    ms_engine& E = *e;
+    REQUIRE(!E.started, MS_EBUSY, "ms_enable_qk_norm comes before the first weight load or request");
+    if (E.qk_norm) return MS_OK;
+    HIP_OK(hipSetDevice(E.cfg.device));
+    std::vector<uint16_t> ones(E.D, 0x3C00);  // fp16 1.0
+    for (Layer& Ly : E.layers)
+      for (f16_t** g : {&Ly.q_norm, &Ly.k_norm}) {
+        *g = E.dalloc<f16_t>(E.D);
+        HIP_OK(hipMemcpy(*g, ones.data(), (size_t)E.D * 2, hipMemcpyHostToDevice));
+      }
+    E.qk_norm = true;
+    E.persist_ok = false;  // the persistent step has no norm between its projection and its rotation
+    E.drop_graphs();
+    return MS_OK;
+  });
+}
+
 // where a logical tensor lives: fused fp16 destination + row map, and its K-quant slot
 struct TensorDst {
   f16_t* dst = nullptr;
@@ -836,6 +898,11 @@ static TensorDst tensor_dst(ms_engine& E, int tensor, int layer) {
     case MS_T_FINAL_NORM: t.dst = E.final_norm; t.rows = 1; t.cols = H; break;
     case MS_T_ATTN_NORM: t.dst = E.layers[layer].attn_norm; t.rows = 1; t.cols = H; break;
     case MS_T_FFN_NORM: t.dst = E.layers[layer].ffn_norm; t.rows = 1; t.cols = H; break;
+    case MS_T_Q_NORM:
+    case MS_T_K_NORM:
+      REQUIRE(E.qk_norm, MS_EINVAL, "q_norm / k_norm need ms_enable_qk_norm");
+      t.dst = tensor == MS_T_Q_NORM ? E.layers[layer].q_norm : E.layers[layer].k_norm; t.rows = 1; t.cols = E.D;
+      break;
     case MS_T_WQ:  // rope-permuted rows (map_mul 0)
       t.dst = E.layers[layer].wqkv; t.rows = QD; t.cols = H; t.mul = 0;
       q(&E.lq[layer][QS_QKV], 1, 7, 0, 0, QD); break;
@@ -862,6 +929,7 @@ static TensorDst tensor_dst(ms_engine& E, int tensor, int layer) {
 
 int ms_load_weight(ms_engine* e, int32_t tensor, int32_t layer, const uint16_t* host, int64_t n) {
   if (!e) return MS_EINVAL;
+  e->started = true;
   e->drop_graphs();
   return guarded(e, [&]() -> int {
     ms_engine& E = *e;
@@ -927,6 +995,7 @@ static void load_quant(ms_engine& E, int tensor, int layer, int type, const uint
 int ms_load_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t type, const void* host,
                      int64_t n_bytes) {
   if (!e) return MS_EINVAL;
+  e->started = true;
   e->drop_graphs();
   return guarded(e, [&]() -> int {
     ms_engine& E = *e;
@@ -955,6 +1024,7 @@ int ms_load_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t type, 
 
 int ms_declare_weight_q(ms_engine* e, int32_t tensor, int32_t layer, int32_t type) {
   if (!e) return MS_EINVAL;
+  e->started = true;
   e->drop_graphs();
   return guarded(e, [&]() -> int {
     ms_engine& E = *e;
@@ -1009,6 +1079,7 @@ static int q4_k_m_type(int tensor, int layer, int n_layers) {
 static int init_synthetic_quant(ms_engine* e, uint64_t seed, float scale, float jitter, int all_type,
                                 int base_type = MS_QT_Q4_K) {
   if (!e) return MS_EINVAL;
+  e->started = true;
   e->drop_graphs();
   return guarded(e, [&]() -> int {
     ms_engine& E = *e;
@@ -1065,6 +1136,7 @@ int ms_init_synthetic_q5_k_m(ms_engine* e, uint64_t seed, float scale, float jit
 
 int ms_init_synthetic(ms_engine* e, uint64_t seed, float std_, float jitter) {
   if (!e) return MS_EINVAL;
+  e->started = true;
   e->drop_graphs();
   return guarded(e, [&]() -> int {
     ms_engine& E = *e;
@@ -1116,6 +1188,7 @@ static void submit_seq(ms_engine& E, const int32_t* ids, int32_t n, int32_t num_
   s->prompt.assign(ids, ids + n);
   s->num_predict = num_predict;
   s->flags = flags;
+  E.started = true;
   E.waiting.push_back(std::move(s));
 }
 
@@ -1825,6 +1898,7 @@ int ms_forward_packed(ms_engine* e, const int32_t* ids, const int32_t* lens, int
     REQUIRE(pages <= (int64_t)E.free_pages.size(), MS_ENOSPC, "not enough KV pages");
     for (int64_t i = 0; i < T; ++i) REQUIRE(ids[i] >= 0 && ids[i] < E.V, MS_EINVAL, "token id out of range");
     E.use(E.cp);
+    E.started = true;
     std::vector<Seq> seqs(n_seqs);
     std::vector<Seq*> b;
     int64_t off = 0;

@@ -299,6 +299,25 @@ int ms_op_rmsnorm(const void* x, const void* w, void* y, float* ssq, int32_t row
   });
 }
 
+int ms_op_qk_norm_rope(void* qkv, const float* slabs, int32_t S, int32_t T, int32_t n_heads, int32_t n_kv_heads,
+                       const int32_t* tok_pos, const int32_t* tok_slot, const float* cos_tab, const float* sin_tab,
+                       const void* q_gain, const void* k_gain, float eps, void* k_pool, void* v_pool,
+                       const int32_t* block_table, int32_t max_pages, void* stream) {
+  return op_guard([&] {
+    REQUIRE(qkv && tok_pos && tok_slot && cos_tab && sin_tab && q_gain && k_gain && k_pool && v_pool && block_table,
+            MS_EINVAL, "qk_norm_rope: null operand");
+    REQUIRE(T >= 1 && n_heads >= 1 && n_kv_heads >= 1 && n_heads + n_kv_heads <= 64 && max_pages >= 1, MS_EINVAL,
+            "bad qk_norm_rope shape (at most 64 query+key heads)");
+    REQUIRE(!slabs || (S >= 1 && S <= 8), MS_EINVAL, "qk_norm_rope: 1..8 slabs");
+    REQUIRE(!slabs || !g_op_rs.ssq || g_op_rs.tiles <= 256, MS_EINVAL, "qk_norm_rope row scale: at most 256 tiles");
+    REQUIRE(((uintptr_t)qkv & 3) == 0 && ((uintptr_t)v_pool & 3) == 0, MS_EINVAL, "qk_norm_rope: 4-B aligned rows");
+    KVView kv{(f16_t*)k_pool, (f16_t*)v_pool, block_table, max_pages, n_kv_heads, 0};
+    launch_qk_norm_rope((f16_t*)qkv, slabs, slabs ? S : 0, T, slabs ? g_op_rs : RowScale{}, T, n_heads, n_kv_heads,
+                        tok_pos, tok_slot, cos_tab, sin_tab, (const f16_t*)q_gain, (const f16_t*)k_gain, eps, kv,
+                        (hipStream_t)stream);
+  });
+}
+
 int ms_op_argmax_partials(const void* partials, int32_t rows, int32_t tiles, int32_t* ids, void* stream) {
   return op_guard([&] {
     REQUIRE(partials && ids && rows >= 1 && tiles >= 1, MS_EINVAL, "bad argmax_partials shape");

@@ -18,7 +18,7 @@ MS_OK, MS_EIO, MS_ENOMEM, MS_EBUSY, MS_EINVAL, MS_ENOSPC = 0, -5, -12, -16, -22,
 MS_FINISH_EOS, MS_FINISH_LENGTH, MS_FINISH_ERROR = 1, 2, 3
 MS_FLAG_IGNORE_EOS = 1
 (MS_T_EMBED, MS_T_ATTN_NORM, MS_T_WQ, MS_T_WK, MS_T_WV, MS_T_WO, MS_T_FFN_NORM, MS_T_WGATE,
- MS_T_WUP, MS_T_WDOWN, MS_T_FINAL_NORM, MS_T_LM_HEAD) = range(12)
+ MS_T_WUP, MS_T_WDOWN, MS_T_FINAL_NORM, MS_T_LM_HEAD, MS_T_Q_NORM, MS_T_K_NORM) = range(14)
 MS_EPI_STORE_F16, MS_EPI_ADD_F32, MS_EPI_SWIGLU, MS_EPI_STORE_F32 = range(4)
 MS_EPI_ARGMAX = 5
 # the prefill GEMM dispatch the library starts with (ms_set_gemm_variant; tests restore it)
@@ -43,6 +43,7 @@ EXPORTED = (
     "ms_op_gemv_resid", "ms_op_set_row_scale", "ms_op_gemm_resid", "ms_gemm_resid_tiles",
     "ms_trace_push", "ms_trace_pop", "ms_debug_a2_stamps", "ms_set_persist", "ms_debug_read", "ms_debug_pk_stamps",
     "ms_submit_sampled", "ms_op_sample", "ms_set_gemv_order", "ms_debug_gemv_stamps",
+    "ms_enable_qk_norm", "ms_op_qk_norm_rope",
 )
 
 
@@ -161,6 +162,9 @@ def load_at(path: str, ab: bool = True) -> C.CDLL:
         "ms_debug_pk_stamps": (i32, [vp, i32]),
         "ms_debug_a2_stamps": (i32, [vp, i32]),
         "ms_debug_gemv_stamps": (i32, [vp, i32]),
+        "ms_enable_qk_norm": (i32, [vp]),
+        "ms_op_qk_norm_rope": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp,
+                                     i32, vp]),
     }
     for name, (res, args) in sig.items():
         if ab and not hasattr(lib, name):  # an A/B build may predate the newest op hooks

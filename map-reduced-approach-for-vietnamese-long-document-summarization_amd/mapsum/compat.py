@@ -184,7 +184,9 @@ def gguf_backend(path: str, engine_cls=None, params: dict | None = None) -> MapB
     if engine_cls is None:
         from .engine import Engine as engine_cls
     meta, ts = read_gguf(path)
+    from .template import RENDERERS
     cfg = config_from_gguf(meta).with_(tie_embeddings="output.weight" not in ts)
+    render = RENDERERS[str(meta.get("general.architecture", "llama"))]  # ChatML for a qwen3 model
     tok = tokenizer_from_gguf(meta)
     stops = list(cfg.eos_ids)
     for s in (params or {}).get("stop", []):
@@ -194,7 +196,7 @@ def gguf_backend(path: str, engine_cls=None, params: dict | None = None) -> MapB
     del ts
     eng = engine_cls(cfg, eos_ids=tuple(stops[:8]), **_engine_kwargs())
     load_gguf(eng, path)
-    return MapBackend(eng, tok)
+    return MapBackend(eng, tok, template=render)
 
 
 def _default_factory(model_name: str) -> MapBackend:

@@ -31,6 +31,9 @@ class ModelConfig:
     tie_embeddings: bool = True
     bos_id: int = 128000
     eos_ids: tuple = (128001, 128008, 128009)
+    # Qwen3: RMSNorm over each Q head and each K head (gains q_norm / k_norm [head_dim]) between
+    # the QKV projection and RoPE (libmapsum ms_enable_qk_norm)
+    qk_norm: bool = False
 
     def with_(self, **kw) -> "ModelConfig":
         return replace(self, **kw)
@@ -79,4 +82,16 @@ LLAMA32_3B = ModelConfig(name="llama3.2-3b", n_layers=28, hidden=3072, n_heads=2
 TINY = ModelConfig(name="tiny", n_layers=2, hidden=768, n_heads=6, n_kv_heads=2, head_dim=128,
                    ffn=2048, vocab=4096, bos_id=4000, eos_ids=(4001, 4002))
 
-CONFIGS = {c.name: c for c in (LLAMA32_3B, TINY)}
+# Qwen3-8B (the reference pipeline's ``qwen3:8b``, run_full_evaluation_pipeline.py:961-962): the
+# public config -- plain RoPE (no frequency scaling), untied lm_head, per-head Q/K RMSNorm.  Its
+# other sizes (0.6B / 4B / 32B) have hidden != n_heads * 128, which the engine does not take.
+QWEN3_8B = ModelConfig(name="qwen3-8b", n_layers=36, hidden=4096, n_heads=32, n_kv_heads=8, head_dim=128,
+                       ffn=12288, vocab=151936, rope_theta=1e6, rope_factor=0.0, norm_eps=1e-6,
+                       tie_embeddings=False, bos_id=151643, eos_ids=(151645, 151643), qk_norm=True)
+
+# Tiny QK-norm test model: GQA 4:1, untied, plain RoPE at Qwen3's theta.
+TINY_QWEN3 = ModelConfig(name="tiny-qwen3", n_layers=2, hidden=1024, n_heads=8, n_kv_heads=2, head_dim=128,
+                         ffn=2048, vocab=4096, rope_theta=1e6, rope_factor=0.0, norm_eps=1e-6,
+                         tie_embeddings=False, bos_id=4000, eos_ids=(4001, 4002), qk_norm=True)
+
+CONFIGS = {c.name: c for c in (LLAMA32_3B, TINY, QWEN3_8B, TINY_QWEN3)}

@@ -225,6 +225,8 @@ class Engine(RequestQueue):
         h = C.c_void_p()
         L.check(self.lib.ms_create(C.byref(c), C.byref(h)), None, "ms_create")
         self.h = h
+        if getattr(cfg, "qk_norm", False):  # before any weight load: the gains start at 1.0
+            self._chk(self.lib.ms_enable_qk_norm(self.h), "ms_enable_qk_norm")
         self.max_batch, self.max_ctx, self.max_prefill_tokens = max_batch, max_ctx, max_prefill_tokens
         self.device = device
         self._next_tag = 1

@@ -10,7 +10,10 @@ llama.cpp's HF -> GGUF converter permutes the rows of attn_q / attn_k per head s
 rotary pairs are adjacent (``permute``: reshape(n_head, 2, hd/2) -> swap -> flatten).
 The kernels implement HF's rotate-half convention, so those rows are put back here.  A
 row of a quantised matrix is a whole run of blocks, so the same row permutation applies
-to Q4_K / Q5_K / Q6_K / Q8_0 data without dequantising.
+to Q4_K / Q5_K / Q6_K / Q8_0 data without dequantising.  The converter permutes only the llama
+architecture: a ``qwen3`` file keeps HF's row order (NeoX-style RoPE = rotate-half on it), so its
+rows are uploaded as they are, and it carries the per-head gains ``blk.N.attn_q_norm.weight`` /
+``attn_k_norm.weight`` and an ``output.weight`` (untied lm_head), and no ``rope_freqs`` tensor.
 
 Supported: every matrix float (F32 / F16 / BF16, uploaded as fp16 -- the engine's type, so an
 F16 file such as llama3.2:3b-instruct-fp16 loads bit for bit), every matrix Q4_K / Q5_K / Q6_K
@@ -158,18 +161,41 @@ def check_rope_freqs(cfg, ts):
                         f"frequency {bad} -- refusing to run this model with another RoPE")
 
 
+ARCHITECTURES = ("llama", "qwen3")
+
+
+def engine_shape_problem(hidden: int, n_heads: int, n_kv_heads: int, head_dim: int, ffn: int, vocab: int):
+    """The first of the engine's shape checks (csrc/engine.cpp validate_config, same wording) that a
+    model's shape fails, or None.  Qwen3-0.6B / 4B / 32B fail "hidden must equal n_heads*head_dim"."""
+    checks = ((head_dim == 128, "head_dim must be 128"),
+              (n_heads > 0 and n_kv_heads > 0 and n_heads % n_kv_heads == 0, "bad head/layer counts"),
+              (n_kv_heads > 0 and n_heads // max(n_kv_heads, 1) <= 16, "GQA group must be <= 16"),
+              (n_heads + n_kv_heads <= 64, "at most 64 query+key heads"),
+              (hidden == n_heads * head_dim, "hidden must equal n_heads*head_dim"),
+              (hidden % 256 == 0 and ffn % 256 == 0, "hidden and ffn must be multiples of 256"),
+              (vocab % 16 == 0 and vocab > 0, "vocab must be a multiple of 16"))
+    for ok, what in checks:
+        if not ok:
+            return what
+    return None
+
+
 def load_gguf(engine, path: str):
-    """Upload a llama-architecture GGUF into ``engine`` (shape checked against engine.cfg)."""
+    """Upload a llama- or qwen3-architecture GGUF into ``engine`` (shape checked against engine.cfg)."""
     cfg = engine.cfg
     meta, ts = read_gguf(path)
     arch = meta.get("general.architecture", "llama")
-    if arch != "llama":
-        raise GGUFError(f"architecture {arch!r} is not llama")
+    if arch not in ARCHITECTURES:
+        raise GGUFError(f"architecture {arch!r} is not llama or qwen3")
+    qk_norm = arch == "qwen3"
+    if qk_norm != bool(getattr(cfg, "qk_norm", False)):
+        raise GGUFError(f"architecture {arch!r} {'has' if qk_norm else 'has no'} per-head Q/K norm, the engine "
+                        f"config {'has none' if qk_norm else 'has one'} (ModelConfig.qk_norm)")
     for key, want in (("block_count", cfg.n_layers), ("embedding_length", cfg.hidden),
                       ("attention.head_count", cfg.n_heads), ("attention.head_count_kv", cfg.n_kv_heads)):
-        got = meta.get(f"llama.{key}")
+        got = meta.get(f"{arch}.{key}")
         if got is not None and int(got) != want:
-            raise GGUFError(f"llama.{key} = {got}, engine config has {want}")
+            raise GGUFError(f"{arch}.{key} = {got}, engine config has {want}")
 
     def get(name):
         if name not in ts:
@@ -183,7 +209,8 @@ def load_gguf(engine, path: str):
     for i in range(cfg.n_layers):
         for g, n in _LAYER.items():
             mats[(i, n)] = get(f"blk.{i}.{g}.weight")
-    heads = {"wq": cfg.n_heads, "wk": cfg.n_kv_heads}
+    # llama.cpp's converter permutes Q / K rows for the llama architecture only
+    heads = {} if qk_norm else {"wq": cfg.n_heads, "wk": cfg.n_kv_heads}
 
     def norm(name):
         t, d, raw = get(name)
@@ -194,6 +221,12 @@ def load_gguf(engine, path: str):
     norms = {"final_norm": norm("output_norm.weight"),
              "layers": [{"attn_norm": norm(f"blk.{i}.attn_norm.weight"),
                          "ffn_norm": norm(f"blk.{i}.ffn_norm.weight")} for i in range(cfg.n_layers)]}
+    if qk_norm:
+        for i, ly in enumerate(norms["layers"]):
+            for key, name in (("q_norm", "attn_q_norm"), ("k_norm", "attn_k_norm")):
+                ly[key] = norm(f"blk.{i}.{name}.weight")
+                if ly[key].size != cfg.head_dim:
+                    raise GGUFError(f"blk.{i}.{name}.weight has {ly[key].size} elements, head_dim is {cfg.head_dim}")
     quant = {k: v[0] in QBLOCK for k, v in mats.items()}
     if all(quant.values()):
         q8 = {k: v[0] == GGML_Q8_0 for k, v in mats.items()}

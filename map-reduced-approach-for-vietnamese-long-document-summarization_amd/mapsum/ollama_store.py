@@ -76,11 +76,17 @@ class OllamaModel:
 LLAMA3_TEMPLATE_MARKERS = ("<|start_header_id|>", "<|end_header_id|>", "<|eot_id|>")
 
 
-def template_problems(text: str) -> list:
-    """Why a manifest's chat template is not the llama3 family the engine renders (empty: it is).
-    The layer is Go template source, so the check is structural: Llama-3's header / end-of-turn
-    markers and a prompt or messages action."""
-    out = [f"no {m!r}" for m in LLAMA3_TEMPLATE_MARKERS if m not in text]
+# ... and a ChatML template for mapsum.template.render_chatml (qwen3 models)
+CHATML_TEMPLATE_MARKERS = ("<|im_start|>", "<|im_end|>")
+
+
+def template_problems(text: str, arch: str = "llama") -> list:
+    """Why a manifest's chat template is not the family the engine renders for a model of this
+    architecture (empty: it is): llama3's for llama, ChatML for qwen3.  The layer is Go template
+    source, so the check is structural: the family's header / end-of-turn markers and a prompt or
+    messages action."""
+    markers = CHATML_TEMPLATE_MARKERS if arch == "qwen3" else LLAMA3_TEMPLATE_MARKERS
+    out = [f"no {m!r}" for m in markers if m not in text]
     if ".Prompt" not in text and ".Messages" not in text:
         out.append("no .Prompt / .Messages action")
     return out
@@ -111,10 +117,16 @@ def resolve(name: str, root: str | None = None, allow_foreign_template: bool = F
     if not out.gguf:
         raise OllamaStoreError(f"manifest {man} has no {MODEL_MEDIA} layer")
     if out.template is not None:
-        why = template_problems(out.template)
+        arch = "llama"
+        if os.path.isfile(out.gguf):  # the template family follows the model's architecture
+            from .gguf import read_gguf
+            arch = str(read_gguf(out.gguf)[0].get("general.architecture", "llama"))
+        why = template_problems(out.template, arch)
         if why and not (allow_foreign_template or os.environ.get("MAPSUM_ALLOW_TEMPLATE") == "1"):
-            raise OllamaStoreError(f"model {name!r}: its chat template is not Llama-3's ({'; '.join(why)}); "
-                                   "the engine renders Llama-3.2's template (mapsum/template.py) -- refusing "
+            family = "ChatML" if arch == "qwen3" else "Llama-3's"
+            raise OllamaStoreError(f"model {name!r}: its chat template is not {family} ({'; '.join(why)}); "
+                                   f"the engine renders {family.replace(chr(39) + 's', '')} for a {arch} model "
+                                   "(mapsum/template.py) -- refusing "
                                    "(MAPSUM_ALLOW_TEMPLATE=1 overrides)")
     if not os.path.isfile(out.gguf):
         raise OllamaStoreError(f"model blob {out.gguf} missing (ollama pull {name})")
@@ -125,10 +137,15 @@ def config_from_gguf(meta: dict, base=None):
     """ModelConfig of a llama GGUF: shapes from llama.* metadata, vocabulary size from the token
     list, BOS / stop ids from tokenizer.ggml.*; the llama3 RoPE scaling constants (not in the
     metadata: Ollama ships them as the rope_freqs tensor) are Llama-3.2's (config.LLAMA32_3B)."""
-    from .config import LLAMA32_3B
+    from .config import LLAMA32_3B, QWEN3_8B
+    from .gguf import ARCHITECTURES, GGUFError, engine_shape_problem
     from .tokenizer import gguf_stop_ids
-    base = base or LLAMA32_3B
-    g = lambda k, d: meta.get(f"llama.{k}", d)  # noqa: E731
+    arch = str(meta.get("general.architecture", "llama"))
+    if arch not in ARCHITECTURES:
+        raise GGUFError(f"architecture {arch!r} is not llama or qwen3")
+    # a qwen3 file: the same key names under qwen3.*, plain RoPE, per-head Q/K norm (config.QWEN3_8B)
+    base = base or (QWEN3_8B if arch == "qwen3" else LLAMA32_3B)
+    g = lambda k, d: meta.get(f"{arch}.{k}", d)  # noqa: E731
     hidden = int(g("embedding_length", base.hidden))
     heads = int(g("attention.head_count", base.n_heads))
     head_dim = int(g("attention.key_length", hidden // heads))
@@ -144,4 +161,9 @@ def config_from_gguf(meta: dict, base=None):
     stops = gguf_stop_ids(meta)
     if stops:
         kw["eos_ids"] = stops
+    if arch == "qwen3":  # the sizes the engine does not take are refused here, with the check's name
+        why = engine_shape_problem(kw["hidden"], kw["n_heads"], kw["n_kv_heads"], kw["head_dim"], kw["ffn"], kw["vocab"])
+        if why:
+            raise GGUFError(f"qwen3 model {kw['name']!r} (hidden {kw['hidden']}, {kw['n_heads']} / {kw['n_kv_heads']} "
+                            f"heads of {kw['head_dim']}, ffn {kw['ffn']}, vocab {kw['vocab']}): {why}")
     return base.with_(**kw)

@@ -77,3 +77,18 @@ STOP_STRINGS = ("<|start_header_id|>", "<|end_header_id|>", "<|eot_id|>")
 
 def render_llama32(prompt: str, add_bos: bool = True) -> str:
     return (BOS if add_bos else "") + LLAMA32_TEMPLATE.replace("{prompt}", prompt)
+
+
+# EXT: ChatML as Ollama's qwen3 TEMPLATE renders /api/generate without system prompt or tools (not
+# vendored, not pinned: no Qwen3 template exists offline).  Qwen's vocabulary prepends no BOS.
+CHATML_TEMPLATE = "<|im_start|>user\n{prompt}<|im_end|>\n<|im_start|>assistant\n"
+CHATML_STOP_STRINGS = ("<|im_start|>", "<|im_end|>")
+
+
+def render_chatml(prompt: str, add_bos: bool = False) -> str:
+    """``add_bos`` is accepted for the renderers' common signature and ignored: ChatML has none."""
+    return CHATML_TEMPLATE.replace("{prompt}", prompt)
+
+
+# the renderer of a model architecture (GGUF general.architecture)
+RENDERERS = {"llama": render_llama32, "qwen3": render_chatml}

@@ -64,6 +64,10 @@ class Tokenizer:
 PRE_TOKENIZERS = {
     "llama-bpe": (r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*"
                   r"|\s*[\r\n]+|\s+(?!\S)|\s+", True),
+    # Qwen2 / Qwen3 (llama.cpp's published "qwen2" pattern): case-insensitive contractions written
+    # out, digits one at a time, no ignore_merges
+    "qwen2": (r"(?:'[sS]|'[tT]|'[rR][eE]|'[vV][eE]|'[mM]|'[lL][lL]|'[dD])|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}"
+              r"| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+", False),
     "default": (r"'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+", False),
 }
 TOKEN_CONTROL, TOKEN_USER_DEFINED = 3, 4  # llama.cpp token types matched as special tokens
@@ -81,6 +85,10 @@ def tokenizer_from_gguf(meta: dict) -> "Tokenizer":
         raise ValueError(f"GGUF pre-tokenizer {pre!r} is not supported ({sorted(PRE_TOKENIZERS)})")
     pattern, ignore_merges = PRE_TOKENIZERS[pre]
     tokens = list(meta["tokenizer.ggml.tokens"])
+    if pre == "qwen2" and not ("<|im_start|>" in tokens and "<|im_end|>" in tokens):
+        # the family is served through the ChatML renderer, whose markers must be single tokens
+        raise ValueError("GGUF pre-tokenizer 'qwen2' is only supported with a ChatML vocabulary: no "
+                         "<|im_start|> / <|im_end|> token")
     types = list(meta.get("tokenizer.ggml.token_type", [1] * len(tokens)))
     merges = [tuple(m.split(" ", 1)) for m in meta.get("tokenizer.ggml.merges", [])]
     vocab = {}
@@ -109,7 +117,7 @@ def gguf_stop_ids(meta: dict) -> tuple:
         if v is not None and int(v) not in out:
             out.append(int(v))
     tokens = meta.get("tokenizer.ggml.tokens", [])
-    for name in ("<|eot_id|>", "<|eom_id|>", "<|end_of_text|>"):
+    for name in ("<|eot_id|>", "<|eom_id|>", "<|end_of_text|>", "<|im_end|>", "<|endoftext|>"):
         if name in tokens:
             i = tokens.index(name)
             if i not in out:

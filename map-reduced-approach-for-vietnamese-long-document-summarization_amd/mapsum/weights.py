@@ -44,6 +44,9 @@ def load_logical(engine, w: dict):
         up(L.MS_T_WGATE, i, ly["w_gate"])
         up(L.MS_T_WUP, i, ly["w_up"])
         up(L.MS_T_WDOWN, i, ly["w_down"])
+        if "q_norm" in ly:  # QK-norm models (cfg.qk_norm): the per-head gains [head_dim]
+            up(L.MS_T_Q_NORM, i, ly["q_norm"])
+            up(L.MS_T_K_NORM, i, ly["k_norm"])
 
 
 _Q_NAMES = {"embed": L.MS_T_EMBED, "lm_head": L.MS_T_LM_HEAD, "wq": L.MS_T_WQ, "wk": L.MS_T_WK,
@@ -55,7 +58,8 @@ def load_quantized(engine, qw: dict, norms: dict):
     """Upload a quantised model -- K-quant (Q4_K / Q5_K / Q6_K per matrix) or Q8_0 throughout, never
     both in one engine: qw[name] = (ggml_type, uint8 blocks) for "embed"/"lm_head" and
     qw[(layer, name)] for the per-layer matrices (rows of raw ggml blocks, GGUF order after
-    Q/K un-permutation); norms = {"final_norm": f32, "layers": [{"attn_norm", "ffn_norm"}]}."""
+    Q/K un-permutation); norms = {"final_norm": f32, "layers": [{"attn_norm", "ffn_norm"}]}, each
+    layer with "q_norm" / "k_norm" too for a QK-norm model."""
     cfg = engine.cfg
     for key, (qt, blocks) in qw.items():
         layer, name = (0, key) if isinstance(key, str) else key
@@ -64,6 +68,9 @@ def load_quantized(engine, qw: dict, norms: dict):
     for i, ly in enumerate(norms["layers"]):
         engine.load_tensor(L.MS_T_ATTN_NORM, i, f32_to_f16_bits(ly["attn_norm"]))
         engine.load_tensor(L.MS_T_FFN_NORM, i, f32_to_f16_bits(ly["ffn_norm"]))
+        if "q_norm" in ly:
+            engine.load_tensor(L.MS_T_Q_NORM, i, f32_to_f16_bits(ly["q_norm"]))
+            engine.load_tensor(L.MS_T_K_NORM, i, f32_to_f16_bits(ly["k_norm"]))
     if len([k for k in qw if not isinstance(k, str)]) != 7 * cfg.n_layers:
         raise RuntimeError("quantised model is missing per-layer matrices")
 
@@ -78,6 +85,8 @@ _HF_LAYER = {
     "mlp.gate_proj.weight": L.MS_T_WGATE,
     "mlp.up_proj.weight": L.MS_T_WUP,
     "mlp.down_proj.weight": L.MS_T_WDOWN,
+    "self_attn.q_norm.weight": L.MS_T_Q_NORM,
+    "self_attn.k_norm.weight": L.MS_T_K_NORM,
 }
 
 
@@ -115,7 +124,7 @@ def load_hf_state_dict(engine, sd: dict):
         else:
             continue
         seen.add(name)
-    need = 2 + 9 * cfg.n_layers + (0 if cfg.tie_embeddings else 1)
+    need = 2 + (11 if getattr(cfg, "qk_norm", False) else 9) * cfg.n_layers + (0 if cfg.tie_embeddings else 1)
     if len(seen) < need:
         raise RuntimeError(f"checkpoint is missing tensors: got {len(seen)} of {need}")
 
