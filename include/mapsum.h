@@ -319,8 +319,10 @@ int ms_set_gemm_variant(int32_t variant);
 /* tuning/test hook: issue order of the fp16 decode GEMVs that stage X by LDS DMA: 0 = the X
    requests ahead of the weight stream, 1 = the first weight step ahead of them, 2 = that with
    per-wave X slices (no X barrier), -1 = the library's per-shape choice (MS_GEMV_ORDER_DEFAULT,
-   what it starts with).  Every order gives the same bits.  An engine launches whatever is set
-   when it captures its decode graphs. */
+   what it starts with).  Adding 3 loads the weights line-exact (each load instruction reads whole
+   128-byte lines that no other instruction reads), adding 6 does so with non-temporal loads: 3..8
+   are the three issue orders on those two load forms.  Every order gives the same bits.  An engine
+   launches whatever is set when it captures its decode graphs. */
 #define MS_GEMV_ORDER_DEFAULT (-1)
 int ms_set_gemv_order(int32_t order);
 /* tuning/test hook: the quantised GEMVs that have a grid-stride two-stage form (the Q6_K and the

@@ -6,11 +6,42 @@ namespace ms {
 
 __device__ __forceinline__ uint4 ldg16(const void* p) { return *(const uint4*)p; }
 
-// once-read decode weight streams: plain loads (non-temporal ones measured slower on the whole
-// decode step, 2.45 vs 2.29 ms, profiles/r01 v5_nt_stream_ab_rejected)
-// (re-measured round 5 on the current GEMVs: nt weight loads 2.30 vs 2.10 ms per decode step,
-// profiles/r05/v4_attn_ticket_nt_ab3.txt)
+// once-read decode weight streams: plain loads.  Non-temporal ones measured slower on the whole
+// decode step twice (2.45 vs 2.29 ms, profiles/r01 v5_nt_stream_ab_rejected; 2.30 vs 2.10 ms on the
+// round-5 GEMVs, profiles/r05/v4_attn_ticket_nt_ab3.txt) -- both with the pair form of the fp16 GEMV,
+// whose two load instructions each touch half of every 32-B sector of the same sixteen 128-B lines:
+// those runs measured the policy on lines that a second instruction still had to read, not on a
+// stream in which every line has one reader (the line-exact form below; DESIGN.md §7 has what
+// that measured).
 __device__ __forceinline__ uint4 ldw16(const void* p) { return *(const uint4*)p; }
+// the same load with the non-temporal (streaming) cache policy: only for weight lines that this
+// one instruction reads whole (k_gemv.hip's line-exact orders)
+__device__ __forceinline__ uint4 ldw16_nt(const void* p) {
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 v = __builtin_nontemporal_load((const u32x4*)p);
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// Line-exact weight fragments (k_gemv.hip, load forms 1 and 2).  Of the instruction pair that loads
+// one 64-k step of a 16-row tile, instruction A reads rows 0-7 and B rows 8-15, 128 contiguous
+// bytes each: lane (fr, fg) reads row (fr & 7) [+ 8], 16-byte chunk 2 fg + (fr >> 3), so every
+// 128-B line has one reading instruction.  lx_exchange then swaps, per dword, one of the two values
+// between lanes fr and fr ^ 8 (DPP row_ror:8 inside the 16-lane row): the low lane keeps A (its
+// row's even chunk) and takes the partner's A (the odd chunk) for its B; the high lane keeps B and
+// takes the partner's B for its A.  Afterwards lane (fr, fg) holds row fr, bytes [32 fg, 32 fg + 16)
+// in a and [32 fg + 16, 32 fg + 32) in b: the registers of the pair form.  All 64 lanes are active.
+__device__ __forceinline__ void lx_exchange(uint4& a, uint4& b, bool hi) {
+  auto swap = [&](unsigned& A, unsigned& B) {
+    const int send = (int)(hi ? A : B);
+    const unsigned recv = (unsigned)__builtin_amdgcn_update_dpp(send, send, 0x128 /* row_ror:8 */, 0xF, 0xF, false);
+    A = hi ? recv : A;
+    B = hi ? B : recv;
+  };
+  swap(a.x, b.x);
+  swap(a.y, b.y);
+  swap(a.z, b.z);
+  swap(a.w, b.w);
+}
 
 // s_waitcnt immediate for vmcnt(n) with expcnt/lgkmcnt left alone (gfx9 encoding)
 __host__ __device__ constexpr int vmcnt_imm(int n) { return (n & 0xF) | ((n >> 4) << 14) | (0x7 << 4) | (0xF << 8); }

@@ -8,7 +8,10 @@
 //  * every wave issues the loads of its whole K slice (U steps of 64) before its
 //    first MFMA: W straight HBM -> VGPR (no LDS round trip, cdna_hip_programming.md
 //    §5 'GEMV / M <= 16'), 32 contiguous bytes per lane per step, so a wave-instruction
-//    pair covers 16 full 128-B lines; X (tiny, L2-resident) is staged into LDS by DMA (chunk
+//    pair covers 16 full 128-B lines (pair form: each instruction reads half of every line;
+//    line-exact form: each instruction reads eight whole lines, non-temporal where that measured
+//    ahead, and a half-row swap between lanes restores the pair form's registers, gemv_common.h
+//    lx_exchange); X (tiny, L2-resident) is staged into LDS by DMA (chunk
 //    swizzle on the source address), the block's whole image or each wave's own k-slice.
 //    The DMA requests are queued AHEAD of the weight stream (all of it in the parent order,
 //    all but its first step in the weight-first orders, gemv_order below): vmcnt retires in
@@ -111,7 +114,7 @@ __device__ unsigned long long g_gemv_stamps[kGvStampBlocks * kGvStamps];
 // form: per wave MFMAs in u order, then the waves in wave order (gemv_epilogue).
 // rinv_off: LDS byte offset of the deferred-norm factors (gemv_rinv_offset).  (Two
 // 1024-thread gate/up blocks share a CU at <= 64 VGPRs: 58 / 60 without / with the row scale.)
-template <int MT, int NT, int EPI, int U, int XM, bool RS, bool WF, bool STAMP>
+template <int MT, int NT, int EPI, int U, int XM, bool RS, bool WF, bool STAMP, int LX = 0>
 __device__ __forceinline__ void gemv_body(const f16_t* __restrict__ X, const f16_t* __restrict__ W,
                                           void* __restrict__ out, int M, int N, int K, int ldk, int ldo,
                                           int rinv_off, const GemvArgs& ga) {
@@ -137,14 +140,31 @@ __device__ __forceinline__ void gemv_body(const f16_t* __restrict__ X, const f16
   constexpr int kAfterX = WF ? (U - 1) * NT * 2 : U * NT * 2;  // weight loads issued behind the X DMA
 
   uint4 w[U][NT][2];
+  // line-exact forms (LX, gemv_common.h lx_exchange): instruction A / B of a pair reads tile rows
+  // (fr & 7) + 0 / 8, chunk 2 fg + (fr >> 3) of the step's 128 bytes; the row clamps apply to the
+  // row each instruction loads.  LX = 2: non-temporal, every line having this one reader
+  auto wrow_lx = [&](int n, int half) {
+    const int r = (fr & 7) + half;
+    const int wrow = NT == 1 ? n0 + min(r, rt - 1) : n0 + n * 16 + r;
+    // the block's 64-bit tile base plus a 32-bit lane offset (< 32 rows): one VGPR per row
+    // pointer, where the form holds twice as many row pointers as the pair form
+    const unsigned off = (unsigned)((min(wrow, N - 1) - n0) * ldk + kbeg + 16 * fg + 8 * (fr >> 3)) * 2u;
+    return (const f16_t*)((const char*)(W + (size_t)n0 * ldk) + off);
+  };
+  auto ldw = [](const f16_t* p) { return LX == 2 ? ldw16_nt(p) : ldw16(p); };
   // weight-first: step u = 0 of every tile leaves ahead of the statistics / residual / X requests
   if constexpr (WF) {
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
-      const int wrow = NT == 1 ? n0 + min(fr, rt - 1) : n0 + n * 16 + fr;
-      const f16_t* wp = W + (size_t)min(wrow, N - 1) * ldk + kbeg + 16 * fg;
-      w[0][n][0] = ldw16(wp);
-      w[0][n][1] = ldw16(wp + 8);
+      if constexpr (LX) {
+        w[0][n][0] = ldw(wrow_lx(n, 0));
+        w[0][n][1] = ldw(wrow_lx(n, 8));
+      } else {
+        const int wrow = NT == 1 ? n0 + min(fr, rt - 1) : n0 + n * 16 + fr;
+        const f16_t* wp = W + (size_t)min(wrow, N - 1) * ldk + kbeg + 16 * fg;
+        w[0][n][0] = ldw16(wp);
+        w[0][n][1] = ldw16(wp + 8);
+      }
     }
     GV_STAMP(2);
     __builtin_amdgcn_sched_barrier(0);
@@ -176,20 +196,26 @@ __device__ __forceinline__ void gemv_body(const f16_t* __restrict__ X, const f16
     for (int u = 1; u < U; ++u)
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
-        const int wrow = NT == 1 ? n0 + min(fr, rt - 1) : n0 + n * 16 + fr;
-        const f16_t* wp = W + (size_t)min(wrow, N - 1) * ldk + kbeg + 16 * fg;
-        w[u][n][0] = ldw16(wp + u * 64);
-        w[u][n][1] = ldw16(wp + u * 64 + 8);
+        if constexpr (LX) {
+          w[u][n][0] = ldw(wrow_lx(n, 0) + u * 64);
+          w[u][n][1] = ldw(wrow_lx(n, 8) + u * 64);
+        } else {
+          const int wrow = NT == 1 ? n0 + min(fr, rt - 1) : n0 + n * 16 + fr;
+          const f16_t* wp = W + (size_t)min(wrow, N - 1) * ldk + kbeg + 16 * fg;
+          w[u][n][0] = ldw16(wp + u * 64);
+          w[u][n][1] = ldw16(wp + u * 64 + 8);
+        }
       }
   } else {
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
       const int wrow = NT == 1 ? n0 + min(fr, rt - 1) : n0 + n * 16 + fr;
-      const f16_t* wp = W + (size_t)min(wrow, N - 1) * ldk + kbeg + 16 * fg;
+      const f16_t* wp = LX ? wrow_lx(n, 0) : W + (size_t)min(wrow, N - 1) * ldk + kbeg + 16 * fg;
+      const f16_t* wq = LX ? wrow_lx(n, 8) : wp + 8;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        w[u][n][0] = ldw16(wp + u * 64);
-        w[u][n][1] = ldw16(wp + u * 64 + 8);
+        w[u][n][0] = ldw(wp + u * 64);
+        w[u][n][1] = ldw(wq + u * 64);
         if (n == 0 && u == 0) GV_STAMP(2);
       }
     }
@@ -207,6 +233,9 @@ __device__ __forceinline__ void gemv_body(const f16_t* __restrict__ X, const f16
     GV_STAMP(6);
     // (two-tile plans fold them at the end: their 6 weight stages fill the 64 VGPRs)
     if constexpr (RS && NT == 1) rs_finish<false>(smem, rinv_off, ga.rs, M, 0.f);
+    // (the exchange of step 0 stays behind the counted wait: hoisted above it, it made the compiler
+    // wait for the whole stream, vmcnt(0), in front of the first MFMA)
+    if constexpr (LX) __builtin_amdgcn_sched_barrier(0);
   }
 
   f32x4 acc[MT][NT];
@@ -227,6 +256,13 @@ __device__ __forceinline__ void gemv_body(const f16_t* __restrict__ X, const f16
         __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
         GV_STAMP(8);
       }
+    }
+    if constexpr (LX) {  // back to the pair form's registers (waits for this step's loads only)
+#pragma unroll
+      for (int n = 0; n < NT; ++n) lx_exchange(w[u][n][0], w[u][n][1], fr >> 3);
+      // two-tile plans: the exchange's temporaries are dead before the X fragments are read (the
+      // six weight stages leave the gate/up GEMV no room for both at once)
+      if constexpr (NT == 2) __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
@@ -378,6 +414,16 @@ __global__ __launch_bounds__(1024) void gemv_wf_kernel(const f16_t* __restrict__
   gemv_body<MT, NT, EPI, U, XM, RS, true, false>(X, W, out, M, N, K, ldk, ldo, rinv_off, ga);
 }
 
+// line-exact weight loads (gemv_body LX: 1 default cache policy, 2 non-temporal) under each issue
+// order of the DMA-staged forms; WF = false is the parent order through the shared body
+template <int MT, int NT, int EPI, int U, int XM, bool RS, bool WF, int LX>
+__global__ __launch_bounds__(1024) void gemv_lx_kernel(const f16_t* __restrict__ X,
+                                                       const f16_t* __restrict__ W,
+                                                       void* __restrict__ out, int M, int N, int K,
+                                                       int ldk, int ldo, int rinv_off, GemvArgs ga) {
+  gemv_body<MT, NT, EPI, U, XM, RS, WF, false, LX>(X, W, out, M, N, K, ldk, ldo, rinv_off, ga);
+}
+
 // the stamped twins of both (M <= 16; never launched unless MS_GEMV_STAMPS=1)
 template <int NT, int EPI, int U, int XM, bool RS, bool WF>
 __global__ __launch_bounds__(1024) void gemv_stamp_kernel(const f16_t* __restrict__ X,
@@ -403,9 +449,13 @@ static bool gemv_stamps_on() {
 
 // Issue order of the DMA-staged decode GEMVs (ms_set_gemv_order / MS_GEMV_ORDER): 0 = X requests
 // first (the parent order), 1 = first weight step first, 2 = that with per-wave X slices; every
-// order gives the same bits.  The library starts on the per-shape table below (-1); a forced
-// order applies to every launch.  MS_GEMV_ORDER is one digit (forced) or one digit per class in
-// the order of the enum (A/B tuning).
+// order gives the same bits.  The weight load form composes with it: order = issue order + 3 x
+// form, form 0 = the pair form (each instruction of a pair reads half of every line of the tile),
+// 1 = line-exact (gemv_common.h lx_exchange), 2 = line-exact with non-temporal loads; so 3..5 and
+// 6..8 are the three issue orders on the line-exact forms.  The library starts on the per-shape
+// table below (-1); a forced order applies to every launch.  MS_GEMV_ORDER is one digit (forced)
+// or one digit per class in the order of the enum (A/B tuning).
+constexpr int kGemvOrders = 9;
 enum { kGcQkv = 0, kGcO, kGcGateUp, kGcDown, kGcLmHead, kGcCount };
 // Measured per shape at M = 8, weights from HBM (tools/gemv_stamps.py --time, us per launch, orders
 // 0 / 1 / 2; profiles/gemv_order/time_ab.txt): O 9.01 / 8.72 / 8.47 and down 15.33 / 14.81 / 14.51
@@ -413,11 +463,19 @@ enum { kGcQkv = 0, kGcO, kGcGateUp, kGcDown, kGcLmHead, kGcCount };
 // their weights ahead of X and stay on the parent order.  Gate/up 22.73 / 22.55 / 22.67 moves
 // inside its own op-level spread; inside the decode step order 1 was ahead in 3 of 3 paired
 // bench rounds (2.0635 vs 2.0694 ms per step, profiles/gemv_order/bench_env_ab.txt), so it takes 1.
-static int g_gemv_class_order[kGcCount] = {0, 2, 1, 2, 0};
+// Load form, same method (profiles/gemv_lines/time_ab.txt, median (min-max) us; a class moves only
+// when its range stays clear of its current default's): the line-exact non-temporal form on per-wave
+// slices (8) takes O 8.16 (8.09-8.42) -> 6.63 (6.52-7.43), down 14.01 (13.90-14.58) -> 12.73
+// (12.58-13.14) and the lm_head 128.45 (128.04-134.10) -> 123.30 (122.59-123.91); gate/up 21.41 ->
+// 19.50 overlaps at op level and was ahead in 3 of 3 in-step pairs (2.0289 vs 2.0453 ms per decode
+// step, bench_env_ab.txt; 63 VGPRs, tests/test_gemv_lines_budget.py).  QKV split-6 reads 12.02
+// (11.82-13.36) -> 10.96 (10.75-12.15) on order 6: the ranges overlap, so it stays on 0.  Line-exact
+// loads under the default policy (3..5) are level with or behind the pair form everywhere.
+static int g_gemv_class_order[kGcCount] = {0, 8, 8, 8, 8};
 static int g_gemv_order = [] {
   const char* e = getenv("MS_GEMV_ORDER");
   if (!e || !e[0]) return -1;
-  auto dig = [](char c) { return c >= '0' && c <= '2' ? c - '0' : 0; };
+  auto dig = [](char c) { return c >= '0' && c < '0' + kGemvOrders ? c - '0' : 0; };
   if (!e[1]) return dig(e[0]);
   for (int i = 0; i < kGcCount && e[i]; ++i) g_gemv_class_order[i] = dig(e[i]);
   return -1;
@@ -434,12 +492,29 @@ static int gemv_order_for(int epi, int N, int U) {
   return 0;
 }
 
-// ord: 0 parent order, 1 weight-first (xm = kXLds or kXWave)
+// sel: the order (issue order + 3 x load form); the issue order is 0 parent order or weight-first
+// (xm = kXLds or kXWave), the line-exact forms exist for the DMA-staged X modes
 template <int MT, int NT, int EPI, int U, bool RS>
 static void gemv_go_rs(const f16_t* X, const f16_t* W, void* out, int M, int N, int K, int ldk,
-                       const dim3& grid, const dim3& blk, size_t lds, int ro, int ldo, int xm, int ord,
+                       const dim3& grid, const dim3& blk, size_t lds, int ro, int ldo, int xm, int sel,
                        const GemvArgs& ga, hipStream_t s) {
+  const int ord = sel % 3, lx = sel / 3;
 #define GL(...) MS_LAUNCH((__VA_ARGS__), grid, blk, lds, s, X, W, out, M, N, K, ldk, ldo, ro, ga)
+  // (built for M <= 16, the batches the decode step runs through these kernels; wider batches
+  // and the stamped twins keep the pair form, which gives the same bits)
+  if constexpr (MT == 1)
+  if (lx && !gemv_stamps_on() && (xm == kXLds || xm == kXWave)) {
+#define GLX(LX_)                                                                     \
+  do {                                                                                 \
+    if (xm == kXWave) GL(gemv_lx_kernel<MT, NT, EPI, U, kXWave, RS, true, LX_>);        \
+    else if (ord) GL(gemv_lx_kernel<MT, NT, EPI, U, kXLds, RS, true, LX_>);             \
+    else GL(gemv_lx_kernel<MT, NT, EPI, U, kXLds, RS, false, LX_>);                     \
+  } while (0)
+    if (lx == 1) GLX(1);
+    else GLX(2);
+#undef GLX
+    return;
+  }
   if constexpr (MT * U <= kXRegsMaxFrags) {
     if (xm == kXRegs) {
       GL(gemv_kernel<MT, NT, EPI, U, kXRegs, RS>);
@@ -550,7 +625,7 @@ static void gemv_dispatch(const f16_t* X, const f16_t* W, void* out, int M, int 
   // the issue order applies to the DMA-staged forms; per-wave slices (whole 8-row pieces) where
   // they fit as well, else the block's image in weight-first order
   const int ord = xl ? gemv_order_for(epi, N, p.U) : 0;
-  if (ord == 2 && gemv_lds_bytes(p, M, K, kXWave, ga.rs) <= kMaxLds) xm = kXWave;
+  if (ord % 3 == 2 && gemv_lds_bytes(p, M, K, kXWave, ga.rs) <= kMaxLds) xm = kXWave;
   if (gemv_x_regs_for(epi) && p.MT * p.U <= kXRegsMaxFrags) xm = kXRegs;
   if (ga.rs.ssq && rs_stage_floats(ga.rs, M) == 0) return;  // callers check gemv_rs_supported
   const size_t lds = gemv_lds_bytes(p, M, K, xm, ga.rs);

@@ -106,7 +106,7 @@ int ms_op_gemm_resid(const void* A, const void* W, float* x, void* xg_out, const
 int ms_gemm_resid_tiles(int32_t M, int32_t N) { return gemm_resid_tiles(M, N); }
 
 int ms_set_gemm_variant(int32_t v) { return checked(v >= 0 && v <= 4, [&] { set_gemm_variant(v); }); }
-int ms_set_gemv_order(int32_t order) { return checked(order >= -1 && order <= 2, [&] { set_gemv_order(order); }); }
+int ms_set_gemv_order(int32_t order) { return checked(order >= -1 && order <= 8, [&] { set_gemv_order(order); }); }
 int ms_set_attn_tuning(int32_t combine_grp, int32_t order) {
   return checked(combine_grp >= 0 && combine_grp <= 1 && (order == 0 || order == 3),
                  [&] { set_attn_tuning(combine_grp, order); });
@@ -136,7 +136,9 @@ int ms_op_gemv(const void* X, const void* W, void* out, int32_t M, int32_t N, in
 int ms_op_gemv_tuned(const void* X, const void* W, void* out, int32_t M, int32_t N, int32_t K,
                      int32_t ldo, int32_t epi, void* ws, int32_t waves, void* stream) {
   return op_guard([&] {
-    REQUIRE(X && W && out && ws && N >= 16 && N % 16 == 0, MS_EINVAL, "bad gemv operands");
+    // (the plain stores take a ragged last tile: its rows are clamped on load and masked in the epilogue)
+    const bool ragged_ok = epi == MS_EPI_STORE_F16 || epi == MS_EPI_STORE_F32;
+    REQUIRE(X && W && out && ws && N >= 16 && (N % 16 == 0 || ragged_ok), MS_EINVAL, "bad gemv operands");
     REQUIRE(((epi >= 0 && epi <= 3) || epi == MS_EPI_ARGMAX) && (epi != MS_EPI_SWIGLU || N % 32 == 0),
             MS_EINVAL, "bad epilogue");
     REQUIRE(gemv_supported(M, N, K, epi, op_rs_tiles()), MS_EINVAL,

@@ -12,6 +12,9 @@ Diagnostic only: the stamped kernels wait for the first and the last weight step
 
   usage: python3 tools/gemv_stamps.py [--orders 0,1,2] [--reps 5]
          python3 tools/gemv_stamps.py --time     (no stamps: us per launch of every shape and order)
+         python3 tools/gemv_stamps.py --time --orders 0,1,2,3,4,5,6,7,8
+           (orders 3..8 = the issue orders on the line-exact weight loads, default policy and
+            non-temporal; timing only: the stamped twins exist for the pair form)
 """
 import argparse
 import ctypes as C
