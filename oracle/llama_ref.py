@@ -171,7 +171,10 @@ class OracleLlama:
         ``"attend"(layer, k, v) -> (k, v)`` edits the [S, Hk, D] keys and values this call attends
         to without touching the cache (one new token only: the causal mask is not re-derived), and
         ``"mask"(layer, mask) -> mask`` edits the [T, S] boolean causal mask (True = hidden) before
-        it is applied (tests/attn_keys_ref.py; every row must keep one visible key)."""
+        it is applied (tests/attn_keys_ref.py; every row must keep one visible key), and
+        ``"rope_q"(layer, q, cos, sin) -> q`` replaces the new tokens' Q rotation (q [T, Hq, D]
+        arrives rounded but un-roped, cos / sin are this call's tables; what it returns is the
+        rotated Q the call attends with: tests/rope_pairs_ref.py)."""
         cfg, w = self.cfg, self.w
         ids = np.asarray(ids, dtype=np.int64)
         T = ids.shape[0]
@@ -214,7 +217,10 @@ class OracleLlama:
             q = pre(r * mm(xg, L["wq"].T)).reshape(T, Hq, D)
             k = pre(r * mm(xg, L["wk"].T)).reshape(T, Hk, D)
             v = rnd(r * mm(xg, L["wv"].T)).reshape(T, Hk, D)
-            q = apply_rope(q, cos, sin, rnd)  # f16: Q rounded for K.Q, K for the F16 cache
+            if "rope_q" in mut:
+                q = mut["rope_q"](l, q, cos, sin)
+            else:
+                q = apply_rope(q, cos, sin, rnd)  # f16: Q rounded for K.Q, K for the F16 cache
             if "new_kv" in mut:
                 k, v = mut["new_kv"](l, k, v)
             else:

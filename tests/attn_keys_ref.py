@@ -15,7 +15,8 @@ oracle and load_logical get the same tensors:
 q(m) . k(n) is therefore large exactly when tokens m and n share a class, wherever they sit; wv, wo and
 the MLP stay random, so two members of one class have equal keys but different values and losing
 either changes the output row completely.  That holds in layer 0; layer 1 reads the residual after
-layer 0 (see "Mutants" below).
+layer 0 (see "Mutants" below).  These queries are blind to the rotation by construction: RoPE itself is
+tested pair by pair in tests/rope_pairs_ref.py, on a model whose scores depend on relative position.
 
 Prompts: position i draws class order[(i + rot) % C] (one fixed permutation, rotated per sequence of
 a pack so that another sequence's K/V hold this row's class at a nearby position) and a random member
