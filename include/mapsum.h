@@ -160,6 +160,20 @@ const char* ms_last_error(const ms_engine* e);
    region.  Such an engine never runs the persistent decode step (ms_set_persist returns 0). */
 int ms_enable_qk_norm(ms_engine* e);
 
+/* q8_0 KV cache (Ollama's OLLAMA_KV_CACHE_TYPE=q8_0): the engine's K/V pools hold ggml Q8_0 blocks -- per
+   (token, kv head) row of 128 fp16 values, 4 blocks of 32 consecutive stored elements, each int8 codes
+   c_i = roundf(t_i / d) with d = amax / 127 in fp32 and the scale stored as fp16 (quantize_row_q8_0_ref;
+   a block with a non-finite value stores the scale NaN and codes 0) -- 60,928 instead of 114,688 bytes
+   per Llama-3.2-3B token.  Pool per (layer, page, kv head): 8192 B of codes int8 [64 tokens][128], then
+   512 B of scales fp16 [64 tokens][4] (8704 B; MS_DBG_KPOOL / MS_DBG_VPOOL return these bytes).
+   Prefill attends over the fp16 K/V of its own pass, so prefill logits and first tokens are those of the
+   fp16-cache engine bit for bit; decode writes the new token quantised and attends over the dequantised
+   cache.  Call after ms_create and before any weight load or request; afterwards it
+   returns MS_EBUSY.  Either order with ms_enable_qk_norm.  Such an engine decodes on the rows route in
+   every regime and never runs the v2 attention, the slab prologue or the persistent decode step
+   (ms_set_persist returns 0).  ms_config and the ABI version are unchanged. */
+int ms_enable_kv_q8_0(ms_engine* e);
+
 /* ---- weights ---------------------------------------------------------------- */
 int ms_load_weight(ms_engine* e, int32_t tensor, int32_t layer, const uint16_t* host_f16,
                    int64_t n_elems);
@@ -254,7 +268,8 @@ int ms_synchronize(ms_engine* e);
 int ms_set_persist(ms_engine* e, int32_t on);
 /* test hook: copy `bytes` from byte `offset` of an engine buffer to host memory (after the
    engine's streams are idle) */
-#define MS_DBG_KPOOL 0          /* K cache [layer][page][kv_head][64][head_dim] fp16 */
+#define MS_DBG_KPOOL 0          /* K cache [layer][page][kv_head][64][head_dim] fp16; a q8_0-KV engine:
+                                   [layer][page][kv_head] slabs of 8704 B (ms_enable_kv_q8_0) */
 #define MS_DBG_VPOOL 1          /* V cache, same layout */
 #define MS_DBG_DECODE_LOGITS 2  /* the decode lm_head output (argmax partials {max, id} per 16 columns;
                                    after a sampling run: the scaled fp32 logits [rows][vocab]) */
@@ -426,6 +441,25 @@ int ms_op_qk_norm_rope(void* qkv, const float* slabs, int32_t S, int32_t T, int3
                        const int32_t* tok_pos, const int32_t* tok_slot, const float* cos_tab, const float* sin_tab,
                        const void* q_gain, const void* k_gain, float eps, void* k_pool, void* v_pool,
                        const int32_t* block_table, int32_t max_pages, void* stream);
+/* The q8_0 KV cache's writer on device operands: fp16 K and V rows [T][n_kv_heads][128], exactly as the
+   fp16 pools would hold them (K after RoPE's rounding), quantised by the engine's own device function into
+   the caller's pools [page][n_kv_heads] x 8704 B (ms_enable_kv_q8_0's layout) at page
+   block_table[tok_slot[t]][tok_pos[t] / 64], offset tok_pos[t] % 64.  Pools 16-B aligned. */
+int ms_op_kv_store_q8_0(const void* k_rows, const void* v_rows, int32_t T, int32_t n_kv_heads, const int32_t* tok_pos,
+                        const int32_t* tok_slot, void* k_pool, void* v_pool, const int32_t* block_table,
+                        int32_t max_pages, void* stream);
+/* Decode attention over q8_0 pools (the engine's rows route): qkv fp16 [B][(n_heads + 2 n_kv_heads) * 128]
+   rows whose Q heads are rotated, natural dim order; seq_len[b] keys (the newest included, already in the
+   pools) of block-table row seq_slot[b] (slot_major != 0: page p of slot s is page s * max_pages + p, no
+   table lookup); max_len >= every seq_len sets the split grid with ppw pages per wave (1..16); workspace of
+   ms_op_attn_decode_q8_0_workspace bytes; out fp16 [B][n_heads * 128].  Runs the attention launch and
+   the split combine.  Scores sum d_K * (q . c) per block in fp32, softmax in fp32, P.V with
+   f16(p * d_V) against the integer codes. */
+int64_t ms_op_attn_decode_q8_0_workspace(int32_t B, int32_t n_heads, int32_t max_len, int32_t ppw);
+int ms_op_attn_decode_q8_0(const void* qkv, int32_t n_heads, int32_t n_kv_heads, const void* k_pool, const void* v_pool,
+                           const int32_t* block_table, int32_t max_pages, int32_t slot_major, const int32_t* seq_len,
+                           const int32_t* seq_slot, int32_t B, int32_t max_len, int32_t ppw, float* workspace,
+                           void* out, void* stream);
 /* ids[r] = argmax_j logits[r][j] (ties -> lowest j; -1 when no logit of the row is finite) */
 int ms_op_argmax(const void* logits, int32_t rows, int32_t n, int32_t* ids, void* stream);
 /* ids[r] = the lowest id of the largest {max, id} partial of row r (MS_EPI_ARGMAX output) */

@@ -37,6 +37,7 @@ static inline int roctxRangePop() { return 0; }
 
 #include "decode_forms.h"
 #include "internal.h"
+#include "kvq8.h"
 
 using namespace ms;
 
@@ -99,6 +100,18 @@ struct ms_engine {
   // per engine, set before the first weight load or request (`started`); every other engine
   // launches exactly what it did without it.
   bool qk_norm = false, started = false;
+  // q8_0 KV cache (ms_enable_kv_q8_0; kvq8.h): the same kind of switch.  The fp16 pools
+  // are replaced by pools of int8 codes + fp16 block scales; prefill attends over the fp16 K/V of its own
+  // pass in a one-layer staging pool (its own block table) while the cache receives their quantisation;
+  // decode takes the rows route in every regime (QKV as fp16 rows, the writer kernel, the q8_0 attention
+  // form) and never the v2 attention, the slab prologue or the persistent step.
+  bool kv_q8 = false;
+  uint8_t *kq8pool = nullptr, *vq8pool = nullptr;
+  size_t layer_kvq8_bytes = 0;
+  f16_t *stage_k = nullptr, *stage_v = nullptr;  // [stage_pages][kv_head][64][128]
+  int stage_pages = 0;
+  int32_t* stage_bt_d = nullptr;  // [max_batch][max_pages], rows of the prompts of the current pass
+  int32_t* stage_bt_h = nullptr;  // pinned
   bool slot_major = false;  // pool of max_batch x max_pages: slot s owns pages [s*max_pages, +max_pages)
   std::vector<void*> allocs;
   std::vector<Layer> layers;
@@ -130,7 +143,9 @@ struct ms_engine {
   }
   void attn_decode(const DecodeQKV& qa, const KVView& kv, const DecodeAttnArgs& da) {
     prof_begin(K_ATTN_DECODE);
-    if (attn2_ok(da.B, da.max_len))
+    if (kv_q8)
+      launch_attn_decode_q8(qa.qkv, attn, Hq, Hk, kvq8_layer(cur_layer), da, attn_ws, stream);
+    else if (attn2_ok(da.B, da.max_len))
       launch_attn_decode2(qa, attn, Hq, Hk, kv, da, attn_ws, S.attn_ppb, stream, S.attn_ticket ? attn_cnt : nullptr);
     else
       launch_attn_decode(qa, attn, Hq, Hk, kv, da, attn_ws, stream);
@@ -270,7 +285,27 @@ struct ms_engine {
     ev_used = 0;
   }
 
+  int cur_layer = 0;  // the layer attn_decode serves (run_layer / run_layer_fused_decode set it)
+  KVQ8View kvq8_layer(int l) const {
+    return KVQ8View{kq8pool + (size_t)l * layer_kvq8_bytes, vq8pool + (size_t)l * layer_kvq8_bytes, bt_d, max_pages, Hk,
+                    slot_major ? 1 : 0};
+  }
+  KVView kv_stage() const { return KVView{stage_k, stage_v, stage_bt_d, max_pages, Hk, 0}; }
+  // RoPE (or the QK-norm kernel) and the K/V scatter of T rows of a q8_0-KV engine: the quantised rows
+  // into the cache, and in a prefill pass the fp16 rows into the staging pool
+  void kv_q8_writer(int l, int T, const int32_t* tok_pos, const int32_t* tok_slot, bool prefill_pass, bool rope_q) {
+    const KVQ8View q8 = kvq8_layer(l);
+    const KVView stage = prefill_pass ? kv_stage() : KVView{};
+    prof_begin(K_MISC);
+    if (qk_norm)
+      launch_qk_norm_rope(qkv, nullptr, 0, 0, RowScale{}, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab,
+                          layers[l].q_norm, layers[l].k_norm, cfg.norm_eps, stage, stream, &q8);
+    else
+      launch_rope_kv_q8(qkv, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab, q8, stage, stream, rope_q);
+    prof_end(K_MISC);
+  }
   KVView kv_layer(int l) const {
+    if (kv_q8) return KVView{};  // no fp16 pools (kvq8_layer / kv_stage)
     KVView v;
     v.k = kpool + (size_t)l * layer_kv_elems;
     v.v = vpool + (size_t)l * layer_kv_elems;
@@ -352,7 +387,7 @@ struct ms_engine {
   // split-K slabs that a residual_rmsnorm launch folds
   bool fused_decode(int B) const {
     if (S.large())
-      return B <= kMaxSlabRows && S.attn_slabs && residual_rmsnorm_supported(kMaxSplit, H) &&
+      return B <= kMaxSlabRows && (S.attn_slabs || kv_q8_rows_ok(B)) && residual_rmsnorm_supported(kMaxSplit, H) &&
              dgemm_supported(B, QKVN, H, S.dsplit_qkv, MS_GEMV_EPI_STORE_F32, 1) &&
              dgemm_supported(B, H, Hq * D, S.dsplit_o, MS_GEMV_EPI_STORE_F32, 1) &&
              dgemm_supported(B, H, F, S.dsplit_down, MS_GEMV_EPI_STORE_F32, 1) &&
@@ -367,13 +402,20 @@ struct ms_engine {
     const int gu_tiles = S.resid_fused(nullptr) ? H / S.resid_rt : 1;
     return residual_rmsnorm_supported(kMaxSplit, H) &&
            (S.attn_slabs ? gemv_split_supported(Bg, QKVN, H, 1)
-                         : gemv_supported(Bg, QKVN, H, qk_norm ? MS_GEMV_EPI_STORE_F16 : MS_GEMV_EPI_ROPE_KV,
-                                          qk_norm ? gu_tiles : 0)) &&
+                         : gemv_supported(Bg, QKVN, H, qk_norm || kv_q8 ? MS_GEMV_EPI_STORE_F16 : MS_GEMV_EPI_ROPE_KV,
+                                          qk_norm || kv_q8 ? gu_tiles : 0)) &&
            gemv_supported(Bg, 2 * F, H, MS_GEMV_EPI_SWIGLU, gu_tiles) &&
            gemv_split_supported(Bg, H, Hq * D, 1) && gemv_split_supported(Bg, H, F, 1) &&
            (!S.resid_fuse || (gemv_supported(Bg, H, Hq * D, MS_GEMV_EPI_RESID_SSQ) &&
                               gemv_supported(Bg, H, F, MS_GEMV_EPI_RESID_SSQ))) &&
            attn_decode_supported(B, Hq, Hk, max_pages * kPage, S.attn_ppw);
+  }
+  // a large-regime q8_0-KV engine: some kernel family stores the QKV projection as fp16 rows with the
+  // one-tile row scale (the rows route; no slabs reach attention)
+  bool kv_q8_rows_ok(int B) const {
+    if (!kv_q8) return false;
+    FormCall c{B, MS_GEMV_EPI_STORE_F16, 1};
+    return pick_form(S, mat(QS_QKV, 0), c).family != F_NONE;
   }
   // a row group's deferred-norm scale: one-tile statistics are per row ([M]), so the group
   // starts at its first row (multi-tile [tiles][M] statistics never reach row groups)
@@ -446,9 +488,18 @@ struct ms_engine {
   void run_layer_fused_decode(int l, int B, const int32_t* tok_pos, const int32_t* tok_slot,
                               const DecodeAttnArgs& da) {
     KVView kv = kv_layer(l);
+    cur_layer = l;
     const RowScale rs_attn = cur_rs;
     DecodeQKV qa{nullptr, slabs, 0, cos_tab, sin_tab, rs_attn};
-    if (qk_norm) {
+    if (kv_q8) {
+      // the rows route in every regime: fp16 QKV rows with the row scale, the writer kernel (rotate,
+      // write Q back, quantise and scatter K/V), then the q8_0 attention form reads the cache
+      GemvArgs ga{};
+      ga.rs = rs_attn;
+      proj(mat(QS_QKV, l), xb, qkv, B, QKVN, MS_GEMV_EPI_STORE_F16, &ga, K_GEMV, sizeof(f16_t));
+      kv_q8_writer(l, B, tok_pos, tok_slot, false, true);
+      qa = DecodeQKV{qkv, nullptr, 0, cos_tab, sin_tab, RowScale{}};
+    } else if (qk_norm) {
       // the GEMV RoPE epilogue and attention's slab prologue cannot see a whole head: the QKV
       // projection is launched as ever (slabs, or fp16 rows with the row scale where the epilogue
       // would run), the norm kernel rotates and scatters, and attention reads rows in every regime
@@ -501,14 +552,20 @@ struct ms_engine {
     // launch: 611 vs 423 + 58 us per layer, scattered 2-byte stores and per-element table loads,
     // profiles/r04/v5_prefill_fusions_prof_*.txt)
     gemm_or_gemv(xb, Ly.wqkv, qkv, T, QKVN, H, QKVN, MS_EPI_STORE_F16, decode, kc, &rs_attn);
-    prof_begin(K_MISC);
+    cur_layer = l;
     // prefill: K / V only -- the attention kernel rotates Q while staging it (pa.cos_tab)
-    if (qk_norm)  // Q too: the norm sits between the projection and the rotation
-      launch_qk_norm_rope(qkv, nullptr, 0, 0, RowScale{}, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab, Ly.q_norm,
-                          Ly.k_norm, cfg.norm_eps, kv, stream);
-    else
-      launch_rope_kv(qkv, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab, kv, stream, decode || !pa.cos_tab);
-    prof_end(K_MISC);
+    if (kv_q8) {
+      kv_q8_writer(l, T, tok_pos, tok_slot, !decode, decode || !pa.cos_tab);
+      if (!decode) kv = kv_stage();  // prefill attends over the fp16 K/V of its own pass
+    } else {
+      prof_begin(K_MISC);
+      if (qk_norm)  // Q too: the norm sits between the projection and the rotation
+        launch_qk_norm_rope(qkv, nullptr, 0, 0, RowScale{}, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab, Ly.q_norm,
+                            Ly.k_norm, cfg.norm_eps, kv, stream);
+      else
+        launch_rope_kv(qkv, T, Hq, Hk, tok_pos, tok_slot, cos_tab, sin_tab, kv, stream, decode || !pa.cos_tab);
+      prof_end(K_MISC);
+    }
     if (decode) {
       attn_decode(DecodeQKV{qkv, nullptr, 0, cos_tab, sin_tab, RowScale{}}, kv, da);
     } else {
@@ -832,6 +889,7 @@ int ms_destroy(ms_engine* e) {
   if (e->first_host) (void)hipHostFree(e->first_host);
   if (e->samp_h) (void)hipHostFree(e->samp_h);
   if (e->bt_h) (void)hipHostFree(e->bt_h);
+  if (e->stage_bt_h) (void)hipHostFree(e->stage_bt_h);
   for (auto& kv : e->decode_graphs) (void)hipGraphExecDestroy(kv.second.first);
   for (auto& pe : e->ev_pairs) {
     (void)hipEventDestroy(pe.start);
@@ -866,6 +924,40 @@ int ms_enable_qk_norm(ms_engine* e) {
       }
     E.qk_norm = true;
     E.persist_ok = false;  // the persistent step has no norm between its projection and its rotation
+    E.drop_graphs();
+    return MS_OK;
+  });
+}
+
+int ms_enable_kv_q8_0(ms_engine* e) {
+  if (!e) return MS_EINVAL;
+  return guarded(e, [&]() -> int {
+    ms_engine& E = *e;
+    REQUIRE(!E.started, MS_EBUSY, "ms_enable_kv_q8_0 comes before the first weight load or request");
+    if (E.kv_q8) return MS_OK;
+    HIP_OK(hipSetDevice(E.cfg.device));
+    // the fp16 pools go; the q8_0 pools (zeroed: stale bytes are finite) and the staging pool come
+    for (f16_t** p : {&E.kpool, &E.vpool}) {
+      E.allocs.erase(std::find(E.allocs.begin(), E.allocs.end(), (void*)*p));
+      HIP_OK(hipFree(*p));
+      *p = nullptr;
+    }
+    E.layer_kvq8_bytes = (size_t)E.n_pages * E.Hk * kKvq8Slab;
+    E.kq8pool = E.dalloc<uint8_t>(E.layer_kvq8_bytes * E.L, true);
+    E.vq8pool = E.dalloc<uint8_t>(E.layer_kvq8_bytes * E.L, true);
+    E.stage_pages = (E.cfg.max_prefill_tokens + kPage - 1) / kPage + E.cfg.max_batch;
+    const size_t stage_elems = (size_t)E.stage_pages * E.Hk * kPage * E.D;
+    E.stage_k = E.dalloc<f16_t>(stage_elems, true);
+    E.stage_v = E.dalloc<f16_t>(stage_elems, true);
+    const size_t bt_n = (size_t)E.cfg.max_batch * E.max_pages;
+    E.stage_bt_d = E.dalloc<int32_t>(bt_n, true);
+    HIP_OK(hipHostMalloc((void**)&E.stage_bt_h, bt_n * sizeof(int32_t), hipHostMallocDefault));
+    std::memset(E.stage_bt_h, 0, bt_n * sizeof(int32_t));
+    E.kv_q8 = true;
+    // the rows route only: no v2 attention, no slab prologue, no persistent step
+    E.S.attn_v2 = false;
+    E.S.attn_slabs = false;
+    E.persist_ok = false;
     E.drop_graphs();
     return MS_OK;
   });
@@ -1374,6 +1466,18 @@ static void prefill(ms_engine& E, std::vector<Seq*>& batch, int n_layers_run, fl
   for (auto& p : qb) a.push_back(p.second);
   int32_t* d = E.upload_args(a);
 
+  if (E.kv_q8) {  // this pass's rows of the staging table: consecutive staging pages per prompt
+    int next = 0;
+    for (Seq* s : batch) {
+      REQUIRE(s->len == 0, MS_EINVAL, "a q8_0-KV engine prefills every prompt whole in one pass");
+      const int need = ((int)s->prompt.size() + kPage - 1) / kPage;
+      REQUIRE(next + need <= E.stage_pages && need <= E.max_pages, MS_ENOSPC, "prefill staging pool too small");
+      int32_t* row = &E.stage_bt_h[(size_t)s->slot * E.max_pages];
+      for (int i = 0; i < need; ++i) row[i] = next++;
+      HIP_OK(hipMemcpyAsync(E.stage_bt_d + (size_t)s->slot * E.max_pages, row, need * sizeof(int32_t),
+                            hipMemcpyHostToDevice, E.stream));
+    }
+  }
   PrefillAttnArgs pa;
   pa.seq_qstart = d + o_qstart;
   pa.seq_qlen = d + o_qlen;
@@ -1853,8 +1957,14 @@ int ms_debug_read(ms_engine* e, int32_t which, int64_t offset, void* host, int64
     const void* base = nullptr;
     size_t cap = 0;
     switch (which) {
-      case MS_DBG_KPOOL: base = E.kpool; cap = E.layer_kv_elems * E.L * sizeof(f16_t); break;
-      case MS_DBG_VPOOL: base = E.vpool; cap = E.layer_kv_elems * E.L * sizeof(f16_t); break;
+      case MS_DBG_KPOOL:
+        base = E.kv_q8 ? (const void*)E.kq8pool : E.kpool;
+        cap = E.kv_q8 ? E.layer_kvq8_bytes * E.L : E.layer_kv_elems * E.L * sizeof(f16_t);
+        break;
+      case MS_DBG_VPOOL:
+        base = E.kv_q8 ? (const void*)E.vq8pool : E.vpool;
+        cap = E.kv_q8 ? E.layer_kvq8_bytes * E.L : E.layer_kv_elems * E.L * sizeof(f16_t);
+        break;
       case MS_DBG_DECODE_LOGITS: base = E.cd.logits; cap = (size_t)E.cfg.max_batch * E.V * sizeof(float); break;
       case MS_DBG_DECODE_X: base = E.cd.x; cap = (size_t)E.cfg.max_batch * E.H * sizeof(float); break;
       case MS_DBG_PREFILL_LOGITS: base = E.cp.logits; cap = (size_t)E.cfg.max_batch * E.V * sizeof(float); break;

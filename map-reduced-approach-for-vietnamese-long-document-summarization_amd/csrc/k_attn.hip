@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "attn_common.h"
+#include "kvq8.h"
 
 namespace ms {
 
@@ -748,6 +749,213 @@ void launch_attn_decode(const DecodeQKV& qa, f16_t* out, int Hq, int Hk, KVView 
   if (qa.slabs) AD(true);
   else AD(false);
 #undef AD
+  launch_combine(ws, out, a.B, Hq, Hk, nsplit, false, s);
+}
+
+// ============================================================ decode over a q8_0 KV cache (kvq8.h)
+// attn_decode_kernel's rows route (Q already rotated in qkv; the new token's K/V were quantised into
+// the cache by the writer kernel before this launch and are read back like any other key: no patch)
+// with the same grid, block geometry, ppw rule, split boundaries, prefetch and partials, on pages of
+// int8 codes + fp16 block scales (8704 B per (page, kv head) for K, the same for V, instead of 16384).
+//   S^T: per 32-element block b one MFMA on the codes as exact fp16 integers (kvq8_codes_f16) into a
+//        zeroed accumulator -- the block's fp32 sum of q_k c_k -- then s += d_K[key][b] * sum in fp32.
+//   P.V: the V scale is folded into P: for the block b of d-tiles 2b, 2b + 1 the B operand is
+//        f16(p[key] * d_V[key][b]) (four P fragments per key step) and the V^T image holds the codes as
+//        fp16 integers -- 64 multiplies and roundings per page and lane where dequantising V on its way
+//        into LDS takes 128 (DESIGN.md §2 states the choice; tests/kv_q8_0_ref.py mirrors it).
+// Keys past len: score -inf, P.d exactly 0 and their V rows zeroed (a stale scale may be NaN).
+template <int PPWT>
+__global__ __launch_bounds__(256, 2) void attn_decode_q8_kernel(const f16_t* __restrict__ qkv, int Hq, int Hk,
+                                                             KVQ8View kv, DecodeAttnArgs a,
+                                                             float* __restrict__ ws, int nsplit, int ppw,
+                                                             float scale_log2) {
+  // [4 waves' V^T images][4 waves x 2 buffers of one page's K | V scales, 1 KiB each]
+  __shared__ __attribute__((aligned(16))) char smem[4 * 16384 + 4 * 2 * kKvq8ScaleImg];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, r = lane & 15;
+  const int b = blockIdx.x, kvh = blockIdx.y, split = blockIdx.z;
+  const int G = Hq / Hk;
+  const int len = a.seq_len[b];
+  const int slot = a.seq_slot[b];
+  const int row_stride = (Hq + 2 * Hk) * kHeadDim;
+  char* vs_ = smem + wave * 16384;
+  char* ss_ = smem + 4 * 16384 + wave * 2 * kKvq8ScaleImg;
+  const int pg0 = split * kSplitPages * ppw + wave;
+  const int pend = min((split + 1) * kSplitPages * ppw, (len + kPage - 1) / kPage);
+  const int32_t* bt = kv.block_table + (size_t)slot * kv.max_pages;
+  constexpr int NWB = kSplitPages;
+
+  // one page in flight: K codes [m-tile][block] of row 16 mt + r and V codes of rows 4 i + g (chunk r)
+  // in registers, and the page's K and V block scales (1 KiB) by ONE LDS DMA into scale buffer `buf`
+  // of this wave.  (The scales in registers too -- 64 more per lane, of keys 16 mt + 4 g .. + 3 for
+  // the S^T rows and the P^T k elements -- spilled 105 registers in the runtime page loop.)
+  // The DMA is issued FIRST: vmcnt retires in order, so the wait at the top of a page (below) and
+  // every compiler wait for a code register cover it.
+  kvq8_u2 kc[4][4], vc[16];
+  auto fetch_k = [&](int pid, int buf) {
+    const uint8_t* slab = kv.k + kvq8_slab(pid, kv.n_kv_heads, kvh);
+    dma16_opaque(kvq8_scales_src(slab, kv.v + kvq8_slab(pid, kv.n_kv_heads, kvh), lane), ss_ + buf * kKvq8ScaleImg);
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int bk = 0; bk < 4; ++bk) kc[mt][bk] = kvq8_fetch_codes8(slab, mt * 16 + r, bk, g);
+  };
+  auto fetch_v = [&](int pid) {
+    const uint8_t* slab = kv.v + kvq8_slab(pid, kv.n_kv_heads, kvh);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) vc[i] = kvq8_fetch_chunk(slab, i * 4 + g, r);
+  };
+  auto page_id = [&](int pg) { return kv.slot_major ? slot * kv.max_pages + pg : bt[pg]; };
+  int pid_next = 0;
+  if constexpr (PPWT == 2) pid_next = pg0 + NWB < pend ? page_id(pg0 + NWB) : 0;
+  if (pg0 < pend) {
+    const int pid0 = page_id(pg0);
+    fetch_k(pid0, 0);
+    fetch_v(pid0);
+  }
+
+  f32x4 o[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -INFINITY, l_run = 0.f;
+
+  if (pg0 < pend) {
+    f16x8 qf[4];
+    {
+      const int hl = min(r, G - 1);
+      const f16_t* qrow = qkv + (size_t)b * row_stride + (kvh * G + hl) * kHeadDim;
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) qf[s4] = as_f16x8(*(const uint4*)(qrow + 32 * s4 + 8 * g));
+    }
+    constexpr int kUnrollPages = PPWT > 0 ? PPWT : 1;
+#pragma unroll kUnrollPages
+    for (int pp = 0; PPWT == 0 || pp < PPWT; ++pp) {
+      const int pg = pg0 + pp * kSplitPages;
+      if (pg >= pend) break;  // wave-uniform
+      const bool more = pg + kSplitPages < pend;
+      // this page's scales (and codes) have landed; the next page's requests come later in the body
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const char* simg = ss_ + (pp & 1) * kKvq8ScaleImg;
+      f32x4 sc[4];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) {
+        const Kvq8Scales4 ksc = kvq8_lds_scales4(simg, false, mt * 16 + 4 * g);
+#pragma unroll
+        for (int bk = 0; bk < 4; ++bk) {
+          const f32x4 t = mfma16(__builtin_bit_cast(f16x8, kvq8_codes_f16(kc[mt][bk])), qf[bk],
+                                 f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float d = kvq8_scale(ksc, j, bk);
+            sc[mt][j] = bk == 0 ? __fmul_rn(d, t[j]) : __fmaf_rn(d, t[j], sc[mt][j]);
+          }
+        }
+      }
+      const int pid_n = PPWT == 2 ? pid_next : (more ? page_id(pg + kSplitPages) : 0);
+      if (more) fetch_k(pid_n, (pp + 1) & 1);  // K registers are free: next page's scales and K in flight
+      float mx = -INFINITY;
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int key = pg * kPage + mt * 16 + 4 * g + j;
+          const float v = (key >= len) ? -INFINITY : sc[mt][j] * scale_log2;
+          sc[mt][j] = v;
+          mx = fmaxf(mx, v);
+        }
+      mx = grp_max(mx);
+      const float m_new = fmaxf(m_run, mx);  // finite: key pg*64 < len is always visible
+      const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
+      float rs = 0.f;
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float p = (sc[mt][j] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(sc[mt][j] - m_new);
+          sc[mt][j] = p;
+          rs += p;
+        }
+      rs = grp_sum(rs);
+      l_run = l_run * alpha + rs;
+      m_run = m_new;
+#pragma unroll
+      for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
+      // V codes -> fp16 integers in this wave's LDS image (rows past len zeroed)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = i * 4 + g;
+        kvq8_u4 w = kvq8_codes_f16(vc[i]);
+        if (pg * kPage + row >= len) w = kvq8_u4{0, 0, 0, 0};
+        *(kvq8_u4*)(vs_ + v_swz(row, r)) = w;
+      }
+      if (more) fetch_v(pid_n);  // V code registers are free: next page's V codes in flight
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the V image is in LDS
+      __builtin_amdgcn_wave_barrier();
+      // P^T of (k-step, block bk) with the V scale folded in, f16(p * d_V), then its two d-tiles
+#pragma unroll
+      for (int kstep = 0; kstep < 2; ++kstep) {
+        const Kvq8Scales4 vsc[2] = {kvq8_lds_scales4(simg, true, (2 * kstep) * 16 + 4 * g),
+                                    kvq8_lds_scales4(simg, true, (2 * kstep + 1) * 16 + 4 * g)};
+#pragma unroll
+        for (int bk = 0; bk < 4; ++bk) {
+          f32x4 pd[2];
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int mt = 2 * kstep + h;
+              const int key = pg * kPage + mt * 16 + 4 * g + j;
+              pd[h][j] = key >= len ? 0.f : __fmul_rn(sc[mt][j], kvq8_scale(vsc[h], j, bk));
+            }
+          const f16x8 pf = pack_p(pd[0], pd[1]);
+#pragma unroll
+          for (int dt = 2 * bk; dt < 2 * bk + 2; ++dt) o[dt] = mfma16(load_vt(vs_, dt, kstep, lane), pf, o[dt]);
+        }
+      }
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  // publish and merge (m, l, O^T) exactly as attn_decode_kernel does
+  {
+    float* mw = (float*)vs_;
+    if (g == 0) { mw[r * 130 + 0] = m_run; mw[r * 130 + 1] = l_run; }
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) mw[r * 130 + 2 + dt * 16 + 4 * g + j] = o[dt][j];
+  }
+  __syncthreads();
+  for (int idx = tid; idx < G * 130; idx += 256) {
+    const int c = idx / 130, k = idx % 130;
+    float M = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) M = fmaxf(M, ((const float*)(smem + w * 16384))[c * 130]);
+    float acc = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float* mw = (const float*)(smem + w * 16384);
+      const float m_w = mw[c * 130];
+      const float f = (m_w == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_w - M);
+      acc += (k == 0) ? 0.f : f * mw[c * 130 + k];
+    }
+    ws[(((size_t)b * Hq + kvh * G + c) * nsplit + split) * 132 + k] = (k == 0) ? M : acc;
+  }
+}
+
+void launch_attn_decode_q8(const f16_t* qkv, f16_t* out, int Hq, int Hk, KVQ8View kv, DecodeAttnArgs a, float* ws,
+                           hipStream_t s) {
+  if (a.B <= 0) return;
+  const int ppw = a.ppw > 0 ? a.ppw : 2;
+  if (!attn_decode_supported(a.B, Hq, Hk, a.max_len, ppw)) return;  // callers check
+  const int nsplit = decode_nsplit(ppw, a.max_len);
+  const float scale_log2 = kLog2e / sqrtf((float)kHeadDim);
+  const dim3 grid(a.B, Hk, nsplit);
+  if (ppw == 2)
+    MS_LAUNCH(attn_decode_q8_kernel<2>, grid, dim3(256), 0, s, qkv, Hq, Hk, kv, a, ws, nsplit, ppw, scale_log2);
+  else
+    MS_LAUNCH(attn_decode_q8_kernel<0>, grid, dim3(256), 0, s, qkv, Hq, Hk, kv, a, ws, nsplit, ppw, scale_log2);
   launch_combine(ws, out, a.B, Hq, Hk, nsplit, false, s);
 }
 

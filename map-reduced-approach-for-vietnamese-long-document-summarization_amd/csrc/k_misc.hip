@@ -5,6 +5,7 @@
 // "ggml op replaced"): get_rows, rms_norm+mul, rope (llama3 freq factors), the greedy
 // sampler.  Numerics contract restated in oracle/llama_ref.py.
 #include "gemv_common.h"
+#include "kvq8.h"
 
 namespace ms {
 
@@ -325,17 +326,25 @@ void launch_residual_rmsnorm(float* x, const float* slabs, int S, const f16_t* w
 // weight rows are uploaded in rope_perm order so a 16-row GEMV tile holds dims i and i+64).
 // rotate-half pairs (i, i+64).  One block per token; the token's Q|K part is staged in LDS
 // first because Q is rewritten in place in natural dim order.
+//
+// Q8 (a q8_0-KV engine, kvq8.h): the rotated K rows and the V rows are collected in LDS and every
+// wave then quantises whole rows into the q8_0 pools through kvq8_store_row.  kv is then the
+// per-pass fp16 STAGING pool of a prefill (its own block table), which receives the fp16 rows as
+// the fp16 cache would, or has kv.k == nullptr (decode: the cache alone).
+template <bool Q8>
 __global__ __launch_bounds__(256) void rope_kv_kernel(f16_t* __restrict__ qkv, int Hq, int Hk,
                                                       const int32_t* __restrict__ tok_pos,
                                                       const int32_t* __restrict__ tok_slot,
                                                       const float* __restrict__ cos_tab,
                                                       const float* __restrict__ sin_tab,
-                                                      KVView kv, int h_begin) {
+                                                      KVView kv, int h_begin, KVQ8View q8) {
   __shared__ __attribute__((aligned(16))) f16_t st[64 * kHeadDim];  // <= 64 Q+K heads
+  // Q8: the K rows, then the V rows, as the fp16 pool would hold them (Hk <= 32)
+  __shared__ __attribute__((aligned(16))) f16_t kvout[Q8 ? 64 * kHeadDim : 8];
   const int t = blockIdx.x;
   const int pos = tok_pos[t];
   const int slot = tok_slot[t];
-  const int page = kv.block_table[(size_t)slot * kv.max_pages + pos / kPage];
+  const int page = !Q8 || kv.k ? kv.block_table[(size_t)slot * kv.max_pages + pos / kPage] : 0;
   const int off = pos % kPage;
   const int row_elems = (Hq + 2 * Hk) * kHeadDim;
   f16_t* row = qkv + (size_t)t * row_elems;
@@ -381,10 +390,27 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(f16_t* __restrict__ qkv, i
     } else {
       const bool is_k = head < Hq + Hk;
       const int kh = is_k ? head - Hq : head - Hq - Hk;
-      f16_t* dst = (is_k ? kv.k : kv.v) +
-                    (((size_t)page * kv.n_kv_heads + kh) * kPage + off) * kHeadDim;
-      *(uint2*)(dst + i0) = olo;
-      *(uint2*)(dst + i0 + 64) = ohi;
+      if constexpr (Q8) {
+        f16_t* o = kvout + (head - Hq) * kHeadDim;
+        *(uint2*)(o + i0) = olo;
+        *(uint2*)(o + i0 + 64) = ohi;
+      }
+      if (!Q8 || kv.k) {
+        f16_t* dst = (is_k ? kv.k : kv.v) +
+                      (((size_t)page * kv.n_kv_heads + kh) * kPage + off) * kHeadDim;
+        *(uint2*)(dst + i0) = olo;
+        *(uint2*)(dst + i0 + 64) = ohi;
+      }
+    }
+  }
+  if constexpr (Q8) {
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int qpage = q8.block_table[(size_t)slot * q8.max_pages + pos / kPage];
+    for (int rw = wave; rw < 2 * Hk; rw += 4) {  // wave-uniform
+      const uint32_t pr = *(const uint32_t*)(kvout + rw * kHeadDim + 2 * lane);
+      uint8_t* slab = (rw < Hk ? q8.k : q8.v) + kvq8_slab(qpage, q8.n_kv_heads, rw < Hk ? rw : rw - Hk);
+      kvq8_store_row(slab, off, h_lo(pr), h_hi(pr), lane);
     }
   }
 }
@@ -393,8 +419,39 @@ void launch_rope_kv(f16_t* qkv, int T, int Hq, int Hk, const int32_t* tok_pos,
                     const int32_t* tok_slot, const float* cos_tab, const float* sin_tab,
                     KVView kv, hipStream_t s, bool rope_q) {
   if (T <= 0) return;
-  MS_LAUNCH(rope_kv_kernel, dim3(T), dim3(256), 0, s, qkv, Hq, Hk, tok_pos, tok_slot,
-                     cos_tab, sin_tab, kv, rope_q ? 0 : Hq);
+  MS_LAUNCH(rope_kv_kernel<false>, dim3(T), dim3(256), 0, s, qkv, Hq, Hk, tok_pos, tok_slot,
+                     cos_tab, sin_tab, kv, rope_q ? 0 : Hq, KVQ8View{});
+}
+
+void launch_rope_kv_q8(f16_t* qkv, int T, int Hq, int Hk, const int32_t* tok_pos, const int32_t* tok_slot,
+                       const float* cos_tab, const float* sin_tab, KVQ8View q8, KVView stage, hipStream_t s,
+                       bool rope_q) {
+  if (T <= 0) return;
+  MS_LAUNCH(rope_kv_kernel<true>, dim3(T), dim3(256), 0, s, qkv, Hq, Hk, tok_pos, tok_slot,
+                     cos_tab, sin_tab, stage, rope_q ? 0 : Hq, q8);
+}
+
+// op-level store (ms_op_kv_store_q8_0): one wave per (token, K or V row of a kv head), rows as the
+// fp16 pool would hold them
+__global__ __launch_bounds__(256) void kv_store_q8_kernel(const f16_t* __restrict__ k, const f16_t* __restrict__ v,
+                                                          int T, int Hk, const int32_t* __restrict__ tok_pos,
+                                                          const int32_t* __restrict__ tok_slot, KVQ8View q8) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int t = blockIdx.x, rw = blockIdx.y * 4 + wave;
+  if (rw >= 2 * Hk) return;  // wave-uniform; no barrier below
+  const int pos = tok_pos[t], slot = tok_slot[t];
+  const int page = q8.block_table[(size_t)slot * q8.max_pages + pos / kPage];
+  const int kh = rw < Hk ? rw : rw - Hk;
+  const f16_t* src = (rw < Hk ? k : v) + ((size_t)t * Hk + kh) * kHeadDim;
+  const uint32_t pr = *(const uint32_t*)(src + 2 * lane);
+  uint8_t* slab = (rw < Hk ? q8.k : q8.v) + kvq8_slab(page, q8.n_kv_heads, kh);
+  kvq8_store_row(slab, pos % kPage, h_lo(pr), h_hi(pr), lane);
+}
+
+void launch_kv_store_q8(const f16_t* k, const f16_t* v, int T, int Hk, const int32_t* tok_pos,
+                        const int32_t* tok_slot, KVQ8View q8, hipStream_t s) {
+  if (T <= 0) return;
+  MS_LAUNCH(kv_store_q8_kernel, dim3(T, (2 * Hk + 3) / 4), dim3(256), 0, s, k, v, T, Hk, tok_pos, tok_slot, q8);
 }
 
 // ---------------------------------------------------------------- greedy argmax

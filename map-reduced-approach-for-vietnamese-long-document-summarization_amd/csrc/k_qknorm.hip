@@ -14,7 +14,11 @@
 //          folded in slab order and rounded f16(rinv * sum) as decode attention's slab prologue does.
 // Both leave Q rotated in natural dim order in its qkv row and K / V at the page and offset of the
 // token's position (V copied as is); the slabs form also leaves the folded fp16 K / V in the row.
+//
+// Q8 (a q8_0-KV engine, kvq8.h), both forms: the K and V rows go through kvq8_store_row into the q8_0
+// pools; kv is then a prefill's fp16 staging pool (it also receives the fp16 rows) or has kv.k null.
 #include "kernels.h"
+#include "kvq8.h"
 
 namespace ms {
 
@@ -30,7 +34,7 @@ __device__ __forceinline__ void qk_head(float lo, float hi, const f16_t* __restr
   rb = __fadd_rn(__fmul_rn(nh, cs), __fmul_rn(nl, sn));
 }
 
-template <bool FROM_SLABS>
+template <bool FROM_SLABS, bool Q8>
 __global__ __launch_bounds__(256) void qk_norm_rope_kernel(f16_t* __restrict__ qkv, const float* __restrict__ slabs,
                                                            int S, int slab_rows, RowScale rs, int T, int Hq, int Hk,
                                                            const int32_t* __restrict__ tok_pos,
@@ -38,7 +42,8 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(f16_t* __restrict__ q
                                                            const float* __restrict__ cos_tab,
                                                            const float* __restrict__ sin_tab,
                                                            const f16_t* __restrict__ q_gain,
-                                                           const f16_t* __restrict__ k_gain, float eps, KVView kv) {
+                                                           const f16_t* __restrict__ k_gain, float eps, KVView kv,
+                                                           KVQ8View q8) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int t = blockIdx.x;
   const int head = blockIdx.y * 4 + wave;
@@ -80,13 +85,19 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(f16_t* __restrict__ q
     hi = h2f(row[e1]);
   }
 
-  const int page = kv.block_table[(size_t)slot * kv.max_pages + pos / kPage];
+  const bool f16_kv = !Q8 || kv.k;  // the fp16 pool (a q8_0-KV engine: its prefill staging pool)
+  const int page = f16_kv ? kv.block_table[(size_t)slot * kv.max_pages + pos / kPage] : 0;
   const int off = pos % kPage;
+  int qpage = 0;
+  if constexpr (Q8) qpage = is_q ? 0 : q8.block_table[(size_t)slot * q8.max_pages + pos / kPage];
   if (!is_q && !is_k) {  // V: copied as is
     const int kh = head - Hq - Hk;
-    f16_t* dst = kv.v + (((size_t)page * kv.n_kv_heads + kh) * kPage + off) * kHeadDim;
     const uint32_t pr = pack2h(lo, hi);  // exact: both are fp16 values
-    *(uint32_t*)(dst + 2 * lane) = pr;
+    if (f16_kv) {
+      f16_t* dst = kv.v + (((size_t)page * kv.n_kv_heads + kh) * kPage + off) * kHeadDim;
+      *(uint32_t*)(dst + 2 * lane) = pr;
+    }
+    if constexpr (Q8) kvq8_store_row(q8.v + kvq8_slab(qpage, q8.n_kv_heads, kh), off, lo, hi, lane);
     if constexpr (FROM_SLABS) *(uint32_t*)(row + 2 * lane) = pr;
     return;
   }
@@ -101,24 +112,43 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(f16_t* __restrict__ q
   qk_head(lo, hi, is_q ? q_gain : k_gain, cs, sn, eps, lane, ra, rb);
   // (every lane's result depends on all 128 loads through the reduction, so the in-place Q
   // stores below cannot pass another lane's load of the same row)
-  f16_t* dst = is_q ? row
-                    : kv.k + (((size_t)page * kv.n_kv_heads + (head - Hq)) * kPage + off) * kHeadDim;
-  dst[lane] = f2h(ra);
-  dst[64 + lane] = f2h(rb);
+  const f16_t ha = f2h(ra), hb = f2h(rb);
+  if (is_q || f16_kv) {
+    f16_t* dst = is_q ? row
+                      : kv.k + (((size_t)page * kv.n_kv_heads + (head - Hq)) * kPage + off) * kHeadDim;
+    dst[lane] = ha;
+    dst[64 + lane] = hb;
+  }
+  if constexpr (Q8) {
+    if (is_k) {  // wave-uniform.  Stored element e sits in lane e % 64 (ha below 64, hb above): lane l
+                 // gathers elements 2l and 2l + 1, the quantiser's order
+      const float fa = h2f(ha), fb = h2f(hb);
+      const int s0 = (2 * lane) & 63;
+      const float a0 = __shfl(fa, s0, 64), a1 = __shfl(fa, s0 + 1, 64);
+      const float b0 = __shfl(fb, s0, 64), b1 = __shfl(fb, s0 + 1, 64);
+      kvq8_store_row(q8.k + kvq8_slab(qpage, q8.n_kv_heads, head - Hq), off, lane < 32 ? a0 : b0,
+                     lane < 32 ? a1 : b1, lane);
+    }
+  }
 }
 
 void launch_qk_norm_rope(f16_t* qkv, const float* slabs, int S, int slab_rows, const RowScale& rs, int T, int Hq,
                          int Hk, const int32_t* tok_pos, const int32_t* tok_slot, const float* cos_tab,
                          const float* sin_tab, const f16_t* q_gain, const f16_t* k_gain, float eps, KVView kv,
-                         hipStream_t s) {
+                         hipStream_t s, const KVQ8View* q8) {
   if (T <= 0) return;
   const dim3 grid(T, (Hq + 2 * Hk + 3) / 4);
-  if (slabs)
-    MS_LAUNCH(qk_norm_rope_kernel<true>, grid, dim3(256), 0, s, qkv, slabs, S, slab_rows, rs, T, Hq, Hk, tok_pos,
-              tok_slot, cos_tab, sin_tab, q_gain, k_gain, eps, kv);
-  else
-    MS_LAUNCH(qk_norm_rope_kernel<false>, grid, dim3(256), 0, s, qkv, slabs, 0, 0, RowScale{}, T, Hq, Hk, tok_pos,
-              tok_slot, cos_tab, sin_tab, q_gain, k_gain, eps, kv);
+#define QN(SL_, Q8_, S_, R_, RS_)                                                                                  \
+  MS_LAUNCH((qk_norm_rope_kernel<SL_, Q8_>), grid, dim3(256), 0, s, qkv, slabs, S_, R_, RS_, T, Hq, Hk, tok_pos, \
+            tok_slot, cos_tab, sin_tab, q_gain, k_gain, eps, kv, Q8_ ? *q8 : KVQ8View{})
+  if (q8) {
+    if (slabs) QN(true, true, S, slab_rows, rs);
+    else QN(false, true, 0, 0, RowScale{});
+  } else {
+    if (slabs) QN(true, false, S, slab_rows, rs);
+    else QN(false, false, 0, 0, RowScale{});
+  }
+#undef QN
 }
 
 }  // namespace ms

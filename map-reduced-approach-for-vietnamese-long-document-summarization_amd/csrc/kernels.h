@@ -16,6 +16,8 @@ struct KVView {
   int32_t slot_major;
 };
 
+struct KVQ8View;  // the q8_0 KV cache (kvq8.h)
+
 // Prefill attention work description (device arrays, see engine.cpp StepArgs).
 constexpr int kPrefillQRows = 128;  // query rows per prefill attention block (8 waves x 16)
 struct PrefillAttnArgs {
@@ -100,14 +102,15 @@ void launch_rope_kv(f16_t* qkv, int T, int Hq, int Hk, const int32_t* tok_pos,
 void launch_argmax(const float* logits, int rows, int n, int32_t* out, hipStream_t s);
 // QK-norm models (k_qknorm.hip): per-head RMSNorm of Q and K (fp16 gains [128], logical dim
 // order) + RoPE in fp32, rounded once; Q rotated in place (natural dim order), K / V into the
-// paged cache -- launch_rope_kv's job with the norm in front.  slabs == nullptr: the rows form on
+// paged cache -- launch_rope_kv's job with the norm in front.  q8 (a q8_0-KV engine, kvq8.h): K / V are
+// quantised into its pools, and kv is the fp16 staging pool of a prefill or has kv.k == nullptr.  slabs == nullptr: the rows form on
 // fp16 qkv [T][..].  Else the slabs form: S fp32 split-K slabs [S][slab_rows][..] of the QKV
 // projection, folded in slab order and rounded f16(rinv * sum) with rs's statistics
 // [tiles][slab_rows] (tiles <= 256; rs.ssq null: no scale), which also writes the fp16 qkv rows.
 void launch_qk_norm_rope(f16_t* qkv, const float* slabs, int S, int slab_rows, const RowScale& rs, int T, int Hq,
                          int Hk, const int32_t* tok_pos, const int32_t* tok_slot, const float* cos_tab,
                          const float* sin_tab, const f16_t* q_gain, const f16_t* k_gain, float eps, KVView kv,
-                         hipStream_t s);
+                         hipStream_t s, const KVQ8View* q8 = nullptr);
 
 // ---- sampled decoding (k_sample.hip; DESIGN.md "Sampler"): repeat penalty -> top-k -> top-p ->
 // min-p -> temperature -> one counter-based draw per row of stored fp32 logits

@@ -5,6 +5,7 @@
 
 #include "internal.h"
 #include "kernels.h"
+#include "kvq8.h"
 
 using namespace ms;
 
@@ -317,6 +318,45 @@ int ms_op_qk_norm_rope(void* qkv, const float* slabs, int32_t S, int32_t T, int3
     launch_qk_norm_rope((f16_t*)qkv, slabs, slabs ? S : 0, T, slabs ? g_op_rs : RowScale{}, T, n_heads, n_kv_heads,
                         tok_pos, tok_slot, cos_tab, sin_tab, (const f16_t*)q_gain, (const f16_t*)k_gain, eps, kv,
                         (hipStream_t)stream);
+  });
+}
+
+int ms_op_kv_store_q8_0(const void* k_rows, const void* v_rows, int32_t T, int32_t n_kv_heads, const int32_t* tok_pos,
+                        const int32_t* tok_slot, void* k_pool, void* v_pool, const int32_t* block_table,
+                        int32_t max_pages, void* stream) {
+  return op_guard([&] {
+    REQUIRE(k_rows && v_rows && tok_pos && tok_slot && k_pool && v_pool && block_table, MS_EINVAL,
+            "kv_store_q8_0: null operand");
+    REQUIRE(T >= 1 && n_kv_heads >= 1 && max_pages >= 1, MS_EINVAL, "bad kv_store_q8_0 shape");
+    REQUIRE((((uintptr_t)k_rows | (uintptr_t)v_rows) & 3) == 0 && (((uintptr_t)k_pool | (uintptr_t)v_pool) & 15) == 0,
+            MS_EINVAL, "kv_store_q8_0: 4-B aligned rows, 16-B aligned pools");
+    const KVQ8View q8{(uint8_t*)k_pool, (uint8_t*)v_pool, block_table, max_pages, n_kv_heads, 0};
+    launch_kv_store_q8((const f16_t*)k_rows, (const f16_t*)v_rows, T, n_kv_heads, tok_pos, tok_slot, q8,
+                       (hipStream_t)stream);
+  });
+}
+
+int64_t ms_op_attn_decode_q8_0_workspace(int32_t B, int32_t n_heads, int32_t max_len, int32_t ppw) {
+  if (B < 1 || n_heads < 1 || max_len < 1 || ppw < 1 || ppw > 16) return MS_EINVAL;
+  return (int64_t)B * n_heads * attn_decode_nsplit(ppw, max_len) * 132 * (int64_t)sizeof(float);
+}
+
+int ms_op_attn_decode_q8_0(const void* qkv, int32_t n_heads, int32_t n_kv_heads, const void* k_pool, const void* v_pool,
+                           const int32_t* block_table, int32_t max_pages, int32_t slot_major, const int32_t* seq_len,
+                           const int32_t* seq_slot, int32_t B, int32_t max_len, int32_t ppw, float* workspace,
+                           void* out, void* stream) {
+  return op_guard([&] {
+    REQUIRE(qkv && k_pool && v_pool && block_table && seq_len && seq_slot && workspace && out, MS_EINVAL,
+            "attn_decode_q8_0: null operand");
+    REQUIRE(B >= 1 && max_len >= 1 && max_pages >= (max_len + kPage - 1) / kPage && ppw >= 1 && ppw <= 16, MS_EINVAL,
+            "bad attn_decode_q8_0 shape (1 <= ppw <= 16, max_pages covers max_len)");
+    REQUIRE(n_kv_heads >= 1 && attn_decode_supported(B, n_heads, n_kv_heads, max_len, ppw), MS_EINVAL,
+            "attn_decode_q8_0: group of at most 8 query heads per kv head, at most 127 splits");
+    REQUIRE((((uintptr_t)k_pool | (uintptr_t)v_pool | (uintptr_t)qkv) & 15) == 0, MS_EINVAL,
+            "attn_decode_q8_0: 16-B aligned pools and rows");
+    const KVQ8View kv{(uint8_t*)k_pool, (uint8_t*)v_pool, block_table, max_pages, n_kv_heads, slot_major ? 1 : 0};
+    const DecodeAttnArgs a{seq_len, seq_slot, B, max_len, ppw};
+    launch_attn_decode_q8((const f16_t*)qkv, (f16_t*)out, n_heads, n_kv_heads, kv, a, workspace, (hipStream_t)stream);
   });
 }
 

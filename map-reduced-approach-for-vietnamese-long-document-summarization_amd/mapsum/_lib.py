@@ -44,6 +44,7 @@ EXPORTED = (
     "ms_trace_push", "ms_trace_pop", "ms_debug_a2_stamps", "ms_set_persist", "ms_debug_read", "ms_debug_pk_stamps",
     "ms_submit_sampled", "ms_op_sample", "ms_set_gemv_order", "ms_debug_gemv_stamps",
     "ms_enable_qk_norm", "ms_op_qk_norm_rope",
+    "ms_enable_kv_q8_0", "ms_op_kv_store_q8_0", "ms_op_attn_decode_q8_0", "ms_op_attn_decode_q8_0_workspace",
 )
 
 
@@ -163,6 +164,10 @@ def load_at(path: str, ab: bool = True) -> C.CDLL:
         "ms_debug_a2_stamps": (i32, [vp, i32]),
         "ms_debug_gemv_stamps": (i32, [vp, i32]),
         "ms_enable_qk_norm": (i32, [vp]),
+        "ms_enable_kv_q8_0": (i32, [vp]),
+        "ms_op_kv_store_q8_0": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
+        "ms_op_attn_decode_q8_0_workspace": (i64, [i32, i32, i32, i32]),
+        "ms_op_attn_decode_q8_0": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
         "ms_op_qk_norm_rope": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp,
                                      i32, vp]),
     }

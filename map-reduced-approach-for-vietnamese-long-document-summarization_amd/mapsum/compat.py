@@ -164,13 +164,28 @@ def set_backend_factory(fn):
     _FACTORY = fn
 
 
+def kv_cache_type_from_env() -> str:
+    """MAPSUM_KV_CACHE_TYPE, else Ollama's own OLLAMA_KV_CACHE_TYPE, else "f16"; "f16" or "q8_0"
+    (anything else, "q4_0" included, raises with the accepted values)."""
+    from .engine import check_kv_cache_type
+    for name in ("MAPSUM_KV_CACHE_TYPE", "OLLAMA_KV_CACHE_TYPE"):
+        v = os.environ.get(name, "").strip()
+        if v:
+            try:
+                return check_kv_cache_type(v)
+            except ValueError as e:
+                raise ValueError(f"{name}: {e}") from e
+    return "f16"
+
+
 def _engine_kwargs() -> dict:
     # the decode regime is fixed per engine (DESIGN.md §5), so any max_batch keeps a batched
     # call equal to the same call alone; 64 in flight runs the large-batch regime
     return dict(device=int(os.environ.get("LOCAL_RANK", 0)),
                 max_batch=int(os.environ.get("MAPSUM_MAX_BATCH", 64)),
                 max_ctx=int(os.environ.get("MAPSUM_MAX_CTX", 16384)),
-                max_prefill_tokens=int(os.environ.get("MAPSUM_MAX_PREFILL", 32768)))
+                max_prefill_tokens=int(os.environ.get("MAPSUM_MAX_PREFILL", 32768)),
+                kv_cache_type=kv_cache_type_from_env())
 
 
 def gguf_backend(path: str, engine_cls=None, params: dict | None = None) -> MapBackend:

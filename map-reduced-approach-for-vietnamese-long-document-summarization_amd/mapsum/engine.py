@@ -201,10 +201,24 @@ class RequestQueue:
         return out
 
 
+KV_CACHE_TYPES = ("f16", "q8_0")
+
+
+def check_kv_cache_type(value) -> str:
+    """The KV cache type of an engine, normalised: "f16" (the default) or "q8_0" (Ollama's
+    OLLAMA_KV_CACHE_TYPE spelling).  Anything else -- "q4_0" included -- is refused."""
+    v = str(value).strip().lower()
+    if v not in KV_CACHE_TYPES:
+        raise ValueError(f"kv_cache_type must be one of {', '.join(repr(t) for t in KV_CACHE_TYPES)}; got {value!r} "
+                         f"(q4_0 and every other type have no kernels here)")
+    return v
+
+
 class Engine(RequestQueue):
     def __init__(self, cfg: ModelConfig, device: int = 0, max_batch: int = 8, max_ctx: int = 4096,
-                 max_prefill_tokens: int = 16384, n_pages: int = 0, eos_ids=None):
+                 max_prefill_tokens: int = 16384, n_pages: int = 0, eos_ids=None, kv_cache_type: str = "f16"):
         self.cfg = cfg
+        self.kv_cache_type = check_kv_cache_type(kv_cache_type)
         self.lib = L.load()
         c = L.MsConfig()
         c.abi_version = L.MS_ABI_VERSION
@@ -227,6 +241,8 @@ class Engine(RequestQueue):
         self.h = h
         if getattr(cfg, "qk_norm", False):  # before any weight load: the gains start at 1.0
             self._chk(self.lib.ms_enable_qk_norm(self.h), "ms_enable_qk_norm")
+        if self.kv_cache_type == "q8_0":  # before any weight load: the pools are re-laid
+            self._chk(self.lib.ms_enable_kv_q8_0(self.h), "ms_enable_kv_q8_0")
         self.max_batch, self.max_ctx, self.max_prefill_tokens = max_batch, max_ctx, max_prefill_tokens
         self.device = device
         self._next_tag = 1
